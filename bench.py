@@ -1,11 +1,18 @@
 """SpatialVLA-4B training-step benchmark on MI355X (BASELINE.json metric).
 
-python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank/GPU)
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                     (N>1: launched by torch.distributed.run, one rank/GPU)
 
 One step = forward + backward + DP gradient all-reduce (RCCL) + grad clip + AdamW over one synthetic
 OXE-shaped batch of B=32 episodes per GPU (BASELINE configs[2]/[3]): 224x224 image + 56-token text
 (256 <image> + bos + 41 prompt + "\\n" + 12 action tokens + eos = 312 tokens).  Weights are random
 (no checkpoint offline); inputs are pre-staged in HBM before timing.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line with the `roofline` object (measured inside the
+timed steps).  --dump-outputs DIR then writes what the last timed step left its caller (dump_outputs below) as
+DIR/<name>.npy; the same arguments give the same inputs, so two builds can be compared output for output.  --full
+adds the objects that take runs of their own after the timed region: `fp8`, `gemma2_block`, `cpu_baseline`, `decode`
+(each still switched off by its --no-* option).
 
 Extra objects:
   roofline     — the dominant kernel (the Gemma2 gate/up GeGLU GEMM, M=B*312, N=2*9216, K=2304): every
@@ -42,6 +49,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--config", default="spatialvla_4b", choices=["spatialvla_4b", "tiny"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: fp8, gemma2_block, cpu_baseline, decode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true", help="skip the B=1 decode-latency leg")
     ap.add_argument("--cpu-iters", type=int, default=3)
@@ -316,6 +327,22 @@ def cpu_baseline(cfgd, iters, batches=(1, 2)):
                       % (iters, ", ".join(f"B={B} {per_b[B]:.2f}s/step = {eps[B]:.4f} ep/s" for B in batches), best)}
 
 
+def dump_outputs(path, engine, loss, world, n_sample=1 << 20):
+    """What the last timed train_step left its caller, as float32 DIR/<name>.npy (rank 0's view): the loss it
+    returned, the gradient norm its clip computed, and the same fixed seeded sample of n_sample positions of the
+    flat buffers it wrote in place -- the updated bf16 parameters and, at N=1 (under ZeRO-1 a rank holds only its
+    chunk of the reduced gradients), the gradients.  ~8 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    engine.sync_params()
+    idx = torch.randint(engine.numel, (min(n_sample, engine.numel),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values.to(engine.device)
+    out = {"loss": loss.reshape(1), "grad_norm": engine.gnorm, "params_sample": engine.flat_param[idx]}
+    if world == 1:
+        out["grads_sample"] = engine.flat_grad[idx]
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: run this script under torch.distributed.run with one rank
     per GPU as a child process (nothing here has touched the GPU yet) and return its exit code."""
@@ -397,6 +424,8 @@ def main():
         dist.all_gather(dts, torch.tensor([dt], dtype=torch.float64, device=device))
         per_rank = [float(t.item()) for t in dts]
     dt = max(per_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, losses[-1], world)
     final_loss = float(losses[-1].item())
     ms_step = dt / args.steps * 1e3
     eps = world * B * args.steps / dt
@@ -417,17 +446,17 @@ def main():
         result["per_rank_seconds"] = [round(t, 6) for t in per_rank]
         result["timed_seconds_max"] = round(dt, 6)
         result["backend"] = args.backend
-    if world == 1 and not args.fp8 and not args.no_fp8_leg and args.config == "spatialvla_4b":
+    if args.full and world == 1 and not args.fp8 and not args.no_fp8_leg and args.config == "spatialvla_4b":
         result["fp8"] = fp8_leg(model, engine, batches, args)
     if rank == 0:
         result["roofline"] = dominant_kernel_roofline(geglu_events, fp8=args.fp8)
-        if args.config == "spatialvla_4b":
+        if args.full and args.config == "spatialvla_4b":
             result["gemma2_block"] = gemma2_block_roofline(model, B, 312, device)
-        if world == 1 and not args.no_cpu_baseline and not args.fp8:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.fp8:
             del batches, engine
             torch.cuda.empty_cache()
             result["cpu_baseline"] = cpu_baseline(cfgd, args.cpu_iters)
-        if world == 1 and args.config == "spatialvla_4b" and not args.no_decode and not args.fp8:
+        if args.full and world == 1 and args.config == "spatialvla_4b" and not args.no_decode and not args.fp8:
             result["decode"] = decode_latency(model, cfgd, device)
         print(json.dumps(result), flush=True)
     if world > 1:

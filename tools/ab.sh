@@ -2,7 +2,7 @@
 # Same-box A/B driver (one script for what the round-4..7 one-off r*_ab.sh scripts did):
 #   TAG=r8a AB_TESTS="tests/test_decode_gpu.py" tools/ab.sh MODE ROUNDS "CFG" ["CFG" ...]
 # MODE    decode  tools/decode_bench.py            -> ms per decode token
-#         step    bench.py --steps 8 --warmup 2    -> ms per step, Gemma2 block ms
+#         step    bench.py --full --steps 8 --warmup 2 -> ms per step, Gemma2 block ms
 #         block   tools/block_ab.py 1 1 5 (isolated Gemma2 block) -> its summary line
 # CFG     space-separated VAR=value assignments applied to the run ("SVLA_LIB=diag/libsvla_x.so SVLA_DECODE_MLP_COOP=0"),
 #         "-" for the defaults.  Configurations alternate within each round, so box drift hits every arm alike.
@@ -36,7 +36,7 @@ for r in $(seq 1 "$ROUNDS"); do
         run_cfg "$cfg" timeout -k 10 300 python -u tools/decode_bench.py --no-uncached > "$f.json" 2> "$f.err" || exit 1
         python -c "import json;d=json.loads(open('$f.json').read().strip().splitlines()[-1]);print('[$cfg]', d['ms_per_decode_token'])" ;;
       step)
-        run_cfg "$cfg" timeout -k 10 400 python -u bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-decode \
+        run_cfg "$cfg" timeout -k 10 400 python -u bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-decode \
           --no-fp8-leg > "$f.json" 2> "$f.err" || exit 1
         python -c "import json;d=json.load(open('$f.json'));print('[$cfg]', d['ms_per_step'], d['gemma2_block']['ms_fwd_bwd'])" ;;
       block)

@@ -19,7 +19,7 @@ if [ -z "$SKIP_TESTS" ]; then
   step pytest 900 python -u -m pytest tests -m gpu -v -s --timeout 600 --timeout-method thread > $O/pytest_gpu.txt 2>&1
   tail -3 $O/pytest_gpu.txt
 fi
-step bench 900 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
+step bench 900 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
 cat $O/bench.json | head -c 3000; echo
 step trace 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o trace --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode --no-fp8-leg > $O/bench_prof.json 2> $O/bench_prof.err
 python tools/summarize_profile.py trace /tmp/prof_$TAG $O/$TAG > $O/trace_summary.log 2>&1
