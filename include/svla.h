@@ -182,6 +182,71 @@ int svla_gemm_fp8(int64_t M, int64_t N, int64_t K, const svla_operand* A, const 
                   const svla_epilogue* epi, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA adapters of the Gemma2 projections (csrc/lora.hip).  Replaces the peft LoRA layers the reference wraps its
+ * linear modules in for fine-tuning -- train/spatialvla_finetune.py:262-300: LoraConfig(r, lora_alpha,
+ * target_modules, init_lora_weights="gaussian"), get_peft_model -- whose forward is base(x) + lora_B(lora_A(x)) * s
+ * with s = lora_alpha / r, for q/k/v/o and gate/up/down (model/modeling_gemma2.py:86-92, 351-354).
+ * A "segment list" is up to 3 small bf16 matrices (one per adapter that shares the large matrix: q|k|v, gate|up), all
+ * of rank r (a multiple of 8, 8..64) and row stride ld, 16-B aligned; each adapter's rank-space slice of T is
+ * R = round_up(r, 32) columns wide: adapter s owns T[:, sR .. sR + r).  `start` (sliced modes): segment s covers
+ * columns [start[s], start[s+1]) of the large matrix, start[0] = 0, start[nseg] = its width.
+ * ---------------------------------------------------------------------------------------- */
+enum { SVLA_LORA_SHARED = 0, SVLA_LORA_SLICED = 1, SVLA_LORA_SUMMED = 2 };
+enum { SVLA_LORA_EPI_NONE = 0, SVLA_LORA_EPI_ROPE = 1, SVLA_LORA_EPI_GEGLU = 2 };
+typedef struct {
+  void* ptr[3];
+  int64_t start[4];
+  int64_t ld;
+  int32_t nseg;
+  int32_t r;
+} svla_lora_segs;
+typedef struct {
+  int32_t kind;
+  int32_t rope_L;            /* ROPE: as svla_epilogue (row m is position m % rope_L, heads of rope_D columns,        */
+  int32_t rope_D;            /*       tables [rope_L][rope_D/2] bf16 with row stride rope_ld, columns < rope_cols)     */
+  int32_t _pad;
+  const void* rope_cos;
+  const void* rope_sin;
+  int64_t rope_ld;
+  int64_t rope_cols;
+  void* h;                   /* GEGLU: second output [M][ldh], N/2 columns */
+  int64_t ldh;
+} svla_lora_epilogue;
+/* T[M, nseg R] (bf16, row stride ldt >= nseg R) from X[M, K] (ldx % 8 == 0, K % 8 == 0), fp32 accumulation, any
+ * M >= 1; columns r..R-1 of every slice are written as zero.  The peft lora_A product and its transpose in backward
+ * (train/spatialvla_finetune.py:262-300):
+ *   SHARED (forward, t = x A^T):  T[m, sR+j] = bf16(alpha sum_k X[m,k] S_s[j,k]),             S_s = A_s [r][K]
+ *   SLICED (backward, dt = s dy B): T[m, sR+j] = bf16(alpha sum_c X[m, start_s+c] S_s[c,j]),  S_s = B_s [N_s][r]
+ * (sliced starts are multiples of 8). */
+int svla_lora_down(int64_t M, int64_t K, const void* x, int64_t ldx, const svla_lora_segs* segs, int32_t mode,
+                   float alpha, void* t, int64_t ldt, void* stream);
+/* In place on C[M, N] bf16 (N % 8 == 0): C = epi(bf16(C + bf16(alpha sum_j T[m, .] S))) -- the bf16 chain of the peft
+ * lora_B product added to the base projection's output (train/spatialvla_finetune.py:262-300):
+ *   SLICED (forward, y += s t B^T): column n of segment s uses T slice s and S_s[n - start_s, j], S_s = B_s [N_s][r]
+ *                                   (starts multiples of 16);
+ *   SUMMED (backward dx += dt A, and the merge W += s B A with C = W, T = B, ldt = r): every column sums over all
+ *                                   segments, sum_s sum_j T[m, sR+j] S_s[j, n], S_s = A_s [r][N].
+ * T has valid width r per slice: no element of a row beyond column r of a slice is read (ldt >= (nseg-1) R + r).
+ * Epilogues: NONE; ROPE = the rotation of SVLA_EPI_ROPE / svla_qkv_rope_fill on columns < rope_cols (same tables,
+ * row -> position rule and rounding points; rope_D % 32 == 0); GEGLU (SLICED, two segments of N/2 columns): C holds
+ * g | u, both stay in place after the update and h = bf16(bf16(gelu_tanh(g)) u) goes to epi->h -- SVLA_EPI_GEGLU's
+ * element formula, so svla_geglu_bwd recomputes the same bits. */
+int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const void* t, int64_t ldt, const svla_lora_segs* segs,
+                 int32_t mode, float alpha, const svla_lora_epilogue* epi, void* stream);
+/* The adapter gradients (autograd of the peft LoRA layer, train/spatialvla_finetune.py:262-300), reduced over the M
+ * rows of Y[M, W] (ldy % 8 == 0, W % 8 == 0) and T[M, nseg R]; outs->ptr[s] are the dense bf16 outputs (outs->ld = W
+ * shared, r sliced), added to when `accumulate`:
+ *   SHARED: dA_s [r][W]   = bf16(alpha sum_m T[m, sR+j] Y[m, c])
+ *   SLICED: dB_s [W_s][r] = bf16(alpha sum_m Y[m, start_s+c] T[m, sR+j])   (starts multiples of 16)
+ * The rows are split over workgroups, fp32 partials go to the caller's workspace (>= svla_lora_wgrad_workspace_bytes,
+ * 16-B aligned, no initialisation needed, one per stream) and a second launch sums them in split order: no block
+ * waits on another, no counters, bitwise stable. */
+size_t svla_lora_wgrad_workspace_bytes(int64_t M, int64_t W, int32_t mode, int32_t nseg, int32_t r);
+int svla_lora_wgrad(int64_t M, int64_t W, const void* y, int64_t ldy, const void* t, int64_t ldt, int32_t mode,
+                    const svla_lora_segs* outs, float alpha, int32_t accumulate, void* workspace, size_t ws_bytes,
+                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via
  * GEMMA2_ATTENTION_FUNCTION (:317-322) with the prefix-LM additive mask of
  * _update_causal_mask (model/modeling_spatialvla.py:258-306) and Gemma2 RoPE

@@ -64,6 +64,19 @@ class ConvArgs(ctypes.Structure):
 
 CONV_PRE_RELU, CONV_POST_RELU, CONV_TRANSPOSED = 1, 2, 4
 
+
+class LoraSegs(ctypes.Structure):
+    _fields_ = [("ptr", c_vp * 3), ("start", c_i64 * 4), ("ld", c_i64), ("nseg", c_i32), ("r", c_i32)]
+
+
+class LoraEpilogue(ctypes.Structure):
+    _fields_ = [("kind", c_i32), ("rope_L", c_i32), ("rope_D", c_i32), ("_pad", c_i32), ("rope_cos", c_vp),
+                ("rope_sin", c_vp), ("rope_ld", c_i64), ("rope_cols", c_i64), ("h", c_vp), ("ldh", c_i64)]
+
+
+LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
+LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU = 0, 1, 2
+
 # name -> (restype, argtypes); every entry point of include/svla.h
 SIGNATURES = {
     "svla_last_error": (ctypes.c_char_p, []),
@@ -87,6 +100,12 @@ SIGNATURES = {
     "svla_gemm_fp8": (c_i32, [c_i64, c_i64, c_i64, ctypes.POINTER(Operand), c_vp, ctypes.POINTER(Operand), c_vp,
                               ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_i64, ctypes.POINTER(Epilogue), c_vp,
                               ctypes.c_size_t, c_vp]),
+    "svla_lora_down": (c_i32, [c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(LoraSegs), c_i32, c_f32, c_vp, c_i64, c_vp]),
+    "svla_lora_up": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(LoraSegs), c_i32, c_f32,
+                             ctypes.POINTER(LoraEpilogue), c_vp]),
+    "svla_lora_wgrad_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    "svla_lora_wgrad": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, ctypes.POINTER(LoraSegs), c_f32, c_i32,
+                                c_vp, ctypes.c_size_t, c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

@@ -847,6 +847,292 @@ class GemmaMLPFn(torch.autograd.Function):
         return dx, retg, retu, ret_wd, None, None, None
 
 
+# ------------------------------------------------------------------------------------ Gemma2 blocks with LoRA adapters
+# The rank-r products of the adapters on the kernels of csrc/lora.hip (SVLA_LORA_KERNELS=0: the same Functions run
+# them as an unfused composition of svla_gemm_bf16 calls and torch elementwise ops -- the A/B partner and a second
+# reference in the tests).
+LORA_KERNELS = [os.environ.get("SVLA_LORA_KERNELS", "1") != "0"]
+# the adapter gradients (svla_lora_wgrad) on the side stream beside the input-gradient chain, as the base weight
+# gradients of the full fine-tune are (_SideWork; results are bitwise the serial order's).  B = 32 4B LoRA step, r = 32,
+# three alternating rounds: 219.4-220.0 ms on the main stream, 212.3-212.8 ms on the side stream
+# (profiles/lora_step.txt); SVLA_LORA_WGRAD_STREAM=0 keeps them on the main stream
+LORA_WGRAD_STREAM = [os.environ.get("SVLA_LORA_WGRAD_STREAM", "1") != "0"]
+
+
+def _rope_torch(c, rope):
+    """In-place rotate_half RoPE of the composition path, the rounding points of SVLA_EPI_ROPE."""
+    cos, sin, Lr, D, cols = rope
+    M = c.shape[0]
+    pos = torch.arange(M, device=c.device) % Lr
+    cs, sn = cos[pos][:, None, :D // 2], sin[pos][:, None, :D // 2]
+    x = c[:, :cols].reshape(M, cols // D, D)
+    x1, x2 = x[..., :D // 2], x[..., D // 2:]
+    lo = x1 * cs + (-x2) * sn  # bf16 tensors: every product and the sum round to bf16
+    hi = x2 * cs + x1 * sn
+    c[:, :cols] = torch.cat([lo, hi], -1).reshape(M, cols)
+
+
+class _LoraKernelOps:
+    """The adapter products on svla_lora_down / svla_lora_up / svla_lora_wgrad."""
+
+    # Two products of a single adapter go to the library's bf16 GEMM instead (a documented choice between two HIP
+    # kernels, DESIGN.md section 4 "LoRA"): t = x A^T with one segment (o: 21.5 us vs 24.5 us on svla_lora_down, down
+    # K = 9216: 70 vs 87 us) and dA = dt^T x with one segment and >= 8192 columns (down: 85 vs 121 us on
+    # svla_lora_wgrad; at 2048 columns the rank-r kernel wins, 46 vs 146 us).  With q|k|v or gate|up sharing the
+    # large matrix the rank-r kernels read it once and win everywhere (profiles/lora_kernels_ab.txt).
+    WGRAD_GEMM_MIN_COLS = 8192
+
+    @staticmethod
+    def down(x, As, r):
+        R = K.lora_R(r)
+        if len(As) == 1:
+            t = _empty(x.shape[0], R, like=x) if r == R else torch.zeros(x.shape[0], R, dtype=BF16, device=x.device)
+            K.linear_fwd(x, [As[0]], t[:, :r])
+            return t
+        t = _empty(x.shape[0], len(As) * R, like=x)
+        K.lora_down(x, As, r, t)
+        return t
+
+    @staticmethod
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None):
+        K.lora_up(c, t, Bs, r, alpha=s, rope=rope, geglu_h=geglu_h)
+
+    @staticmethod
+    def down_t(dy, Bs, r, s):
+        dt = _empty(dy.shape[0], len(Bs) * K.lora_R(r), like=dy)
+        K.lora_down(dy, Bs, r, dt, sliced=True, alpha=s)
+        return dt
+
+    @staticmethod
+    def up_t(dx, dt, As, r):
+        K.lora_up(dx, dt, As, r, summed=True)
+
+    @staticmethod
+    def wgrad(y, t, dests, r, sliced, alpha, starts):
+        R = K.lora_R(r)
+        if (not sliced and len(dests) == 1 and dests[0][0] is not None and alpha == 1.0
+                and y.shape[1] >= _LoraKernelOps.WGRAD_GEMM_MIN_COLS):
+            K.linear_wgrad(_c(t[:, :r]), y, [dests[0][0]], accumulate=dests[0][1])
+            return
+        if all(d[0] is not None for d in dests) and len({d[1] for d in dests}) == 1:
+            K.lora_wgrad(y, t, [d[0] for d in dests], r, sliced=sliced, alpha=alpha, accumulate=dests[0][1])
+            return
+        for i, (g, acc, _) in enumerate(dests):
+            if g is not None:
+                ys = y[:, starts[i]:starts[i + 1]] if sliced else y
+                K.lora_wgrad(ys, t[:, i * R:(i + 1) * R], [g], r, sliced=sliced, alpha=alpha, accumulate=acc)
+
+
+class _LoraComposedOps:
+    """The same products as an unfused composition: svla_gemm_bf16 wrappers plus torch elementwise ops."""
+
+    @staticmethod
+    def down(x, As, r):
+        R = K.lora_R(r)
+        t = torch.zeros(x.shape[0], len(As) * R, dtype=BF16, device=x.device)
+        for i, a in enumerate(As):
+            K.linear_fwd(x, [a], t[:, i * R:i * R + r])
+        return t
+
+    @staticmethod
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None):
+        R = K.lora_R(r)
+        off = 0
+        for i, b in enumerate(Bs):
+            u = _empty(c.shape[0], b.shape[0], like=c)
+            K.linear_fwd(t[:, i * R:i * R + r], [b], u, alpha=s)
+            c[:, off:off + b.shape[0]] += u
+            off += b.shape[0]
+        if rope is not None:
+            _rope_torch(c, rope)
+        if geglu_h is not None:
+            I = c.shape[1] // 2
+            torch.mul(torch.nn.functional.gelu(c[:, :I], approximate="tanh"), c[:, I:], out=geglu_h)
+
+    @staticmethod
+    def down_t(dy, Bs, r, s):
+        R = K.lora_R(r)
+        dt = torch.zeros(dy.shape[0], len(Bs) * R, dtype=BF16, device=dy.device)
+        off = 0
+        for i, b in enumerate(Bs):
+            K.linear_dgrad(dy[:, off:off + b.shape[0]], [b], dt[:, i * R:i * R + r])
+            off += b.shape[0]
+        if s != 1.0:
+            dt *= s
+        return dt
+
+    @staticmethod
+    def up_t(dx, dt, As, r):
+        R = K.lora_R(r)
+        for i, a in enumerate(As):
+            K.linear_dgrad(dt[:, i * R:i * R + r], [a], dx, accumulate=True)
+
+    @staticmethod
+    def wgrad(y, t, dests, r, sliced, alpha, starts):
+        R = K.lora_R(r)
+        for i, (g, acc, _) in enumerate(dests):
+            if g is None:
+                continue
+            tmp = torch.empty_like(g)
+            ti = _c(t[:, i * R:i * R + r])
+            if sliced:   # dB_i [N_i, r] = alpha y_i^T t_i
+                K.linear_wgrad(_c(y[:, starts[i]:starts[i + 1]]), ti, [tmp])
+            else:        # dA_i [r, W] = alpha t_i^T y
+                K.linear_wgrad(ti, y, [tmp])
+            if alpha != 1.0:
+                tmp *= alpha
+            if acc:
+                g += tmp
+            else:
+                g.copy_(tmp)
+
+
+def _lora_ops():
+    return _LoraKernelOps if LORA_KERNELS[0] else _LoraComposedOps
+
+
+def _lora_grads(ops, dy, t, x, r, s, Bs, As, needs):
+    """dt = s dy B (returned), and the adapter gradients dB = s dy^T t, dA = dt^T x written to their destinations;
+    returns (dt, [values for autograd: dA_0, dB_0, dA_1, dB_1, ...])."""
+    sizes = [b.shape[0] for b in Bs]
+    starts = [0]
+    for n in sizes:
+        starts.append(starts[-1] + n)
+    dt = ops.down_t(dy, Bs, r, s)
+    dB = [_grad_dest(b, needs[2 * i + 1]) for i, b in enumerate(Bs)]
+    dA = [_grad_dest(a, needs[2 * i]) for i, a in enumerate(As)]
+    rets = []
+    for a, b in zip(dA, dB):
+        rets += [a[2], b[2]]
+
+    def wgrads():
+        ops.wgrad(dy, t, dB, r, True, s, starts)
+        ops.wgrad(x, dt, dA, r, False, 1.0, starts)
+    if LORA_WGRAD_STREAM[0]:
+        side = _SideWork(x)
+        side.run(wgrads, dy, t, x, dt)
+        side.join(*rets)
+    else:
+        wgrads()
+    return dt, rets
+
+
+def _frozen(ctx, idx, what):
+    if any(ctx.needs_input_grad[i] for i in idx):
+        raise RuntimeError(f"{what}: the base weights of a LoRA-adapted projection must be frozen "
+                           "(requires_grad=False); no base weight gradient is computed")
+
+
+class GemmaAttentionLoRAFn(torch.autograd.Function):
+    """GemmaAttentionFn with a LoRA adapter on each of q, k, v, o (reference train/spatialvla_finetune.py:262-300,
+    peft Linear.forward: base(x) + lora_B(lora_A(x)) * scaling): the base q|k|v GEMM stores plainly, one rank-r pass
+    adds s t B^T and applies RoPE in place; the backward computes the adapter and input gradients only (frozen base)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, wk, wv, wo, cos, sin, kv_class, cfg: GemmaAttnCfg, scaling: float, r: int,
+                Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo):
+        _frozen(ctx, (1, 2, 3, 4), "GemmaAttentionLoRAFn")
+        ops = _lora_ops()
+        x = _c(x)
+        M = x.shape[0]
+        qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
+        t = ops.down(x, [Aq, Ak, Av], r)
+        qkv = _empty(M, qd + 2 * kd, like=x)
+        K.linear_fwd(x, [wq, wk, wv], qkv)
+        ops.up(qkv, t, [Bq, Bk, Bv], r, scaling, rope=(cos, sin, cos.shape[0], cfg.D, qd + kd))
+        attn = _empty(M, qd, like=x)
+        lse = _empty(cfg.B, cfg.Hq, cfg.L, dtype=F32, like=x)
+        a = K.attn_args(cfg.B, cfg.L, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
+                        qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, kv_class, cfg.window)
+        K.attn_fwd(a, attn, lse)
+        t_o = ops.down(attn, [Ao], r)
+        out = _empty(M, wo.shape[0], like=x)
+        K.linear_fwd(attn, [wo], out)
+        ops.up(out, t_o, [Bo], r, scaling)
+        ctx.save_for_backward(x, wq, wk, wv, wo, qkv, attn, lse, cos, sin, kv_class, t, t_o,
+                              Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo)
+        ctx.cfg, ctx.scaling, ctx.r = cfg, scaling, r
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (x, wq, wk, wv, wo, qkv, attn, lse, cos, sin, kv_class, t, t_o,
+         Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo) = ctx.saved_tensors
+        cfg, s, r = ctx.cfg, ctx.scaling, ctx.r
+        if cos.shape[0] != cfg.L:
+            raise NotImplementedError("GemmaAttentionLoRAFn.backward: per-sequence RoPE tables")
+        ops = _lora_ops()
+        dout = _c(dout)
+        M = x.shape[0]
+        qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
+        nig = ctx.needs_input_grad
+        dt_o, g_o = _lora_grads(ops, dout, t_o, attn, r, s, [Bo], [Ao], nig[17:19])
+        dattn = _empty(M, qd, like=x)
+        K.linear_dgrad(dout, [wo], dattn)
+        ops.up_t(dattn, dt_o, [Ao], r)
+        dqkv = torch.empty_like(qkv)
+        a = K.attn_args(cfg.B, cfg.L, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
+                        qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, kv_class, cfg.window,
+                        cos, sin)
+        ld = dqkv.stride(0)
+        K.attn_bwd(a, attn, dattn, lse, dqkv[:, :qd], ld, dqkv[:, qd:qd + kd], ld, dqkv[:, qd + kd:], ld)
+        dt, g_qkv = _lora_grads(ops, dqkv, t, x, r, s, [Bq, Bk, Bv], [Aq, Ak, Av], nig[11:17])
+        dx = None
+        if nig[0]:
+            dx = torch.empty_like(x)
+            K.linear_dgrad(dqkv, [wq, wk, wv], dx)
+            ops.up_t(dx, dt, [Aq, Ak, Av], r)
+        return (dx, None, None, None, None, None, None, None, None, None, None, *g_qkv, *g_o)
+
+
+class GemmaMLPLoRAFn(torch.autograd.Function):
+    """GemmaMLPFn with a LoRA adapter on each of gate, up, down (reference train/spatialvla_finetune.py:262-300): the
+    base gate|up GEMM stores g | u plainly into one [M, 2I] buffer, one rank-r pass adds the adapters and writes
+    h = gelu_tanh(g) u; the down adapter's gradient contribution enters dH before the GeGLU derivative pass."""
+
+    @staticmethod
+    def forward(ctx, x, wg, wu, wd, scaling: float, r: int, Ag, Bg, Au, Bu, Ad, Bd):
+        _frozen(ctx, (1, 2, 3), "GemmaMLPLoRAFn")
+        ops = _lora_ops()
+        x = _c(x)
+        M = x.shape[0]
+        I = wg.shape[0]
+        t = ops.down(x, [Ag, Au], r)
+        gu = _empty(M, 2 * I, like=x)
+        K.linear_fwd(x, [wg, wu], gu)
+        h = _empty(M, I, like=x)
+        ops.up(gu, t, [Bg, Bu], r, scaling, geglu_h=h)
+        t_d = ops.down(h, [Ad], r)
+        out = _empty(M, wd.shape[0], like=x)
+        K.linear_fwd(h, [wd], out)
+        ops.up(out, t_d, [Bd], r, scaling)
+        ctx.save_for_backward(x, wg, wu, wd, gu, h, t, t_d, Ag, Bg, Au, Bu, Ad, Bd)
+        ctx.scaling, ctx.r = scaling, r
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, wg, wu, wd, gu, h, t, t_d, Ag, Bg, Au, Bu, Ad, Bd = ctx.saved_tensors
+        s, r = ctx.scaling, ctx.r
+        ops = _lora_ops()
+        dout = _c(dout)
+        M = x.shape[0]
+        I = wg.shape[0]
+        nig = ctx.needs_input_grad
+        dt_d, g_d = _lora_grads(ops, dout, t_d, h, r, s, [Bd], [Ad], nig[10:12])
+        dgu = _empty(M, 2 * I, like=x)
+        K.linear_dgrad(dout, [wd], dgu[:, :I])
+        ops.up_t(dgu[:, :I], dt_d, [Ad], r)
+        K.geglu_bwd(dgu[:, :I], gu[:, :I], gu[:, I:], dgu[:, :I], dgu[:, I:])
+        dt, g_gu = _lora_grads(ops, dgu, t, x, r, s, [Bg, Bu], [Ag, Au], nig[6:10])
+        dx = None
+        if nig[0]:
+            dx = torch.empty_like(x)
+            K.linear_dgrad(dgu, [wg, wu], dx)
+            ops.up_t(dx, dt, [Ag, Au], r)
+        return (dx, None, None, None, None, None, *g_gu, *g_d)
+
+
 # ------------------------------------------------------------------------------------ SigLIP blocks
 @dataclass
 class SiglipAttnCfg:

@@ -975,6 +975,126 @@ def ceil_div(a: int, b: int) -> int:
     return -(-a // b)
 
 
+# ---------------------------------------------------------------------------------------- LoRA (csrc/lora.hip)
+def lora_R(r: int) -> int:
+    """Width of one adapter's rank-space slice of T."""
+    return round_up(r, 32)
+
+
+def _lora_segs(mats: Sequence[torch.Tensor], r: int, starts=None) -> L.LoraSegs:
+    s = L.LoraSegs()
+    _req(1 <= len(mats) <= 3, f"lora: 1..3 segments, got {len(mats)}")
+    ld = _ld(mats[0])
+    for i, m in enumerate(mats):
+        _chk_bf16(m, "lora segment")
+        _req(_ld(m) == ld, "lora: all segments need the same leading dimension")
+        s.ptr[i] = m.data_ptr()
+    s.nseg, s.r, s.ld = len(mats), int(r), ld
+    if starts is not None:
+        for i, v in enumerate(starts):
+            s.start[i] = int(v)
+    return s
+
+
+def lora_down(x: torch.Tensor, mats: Sequence[torch.Tensor], r: int, t: torch.Tensor, sliced: bool = False,
+              alpha: float = 1.0):
+    """t[M, nseg R] = bf16(alpha x A_s^T) (mats [r, K]), or sliced: bf16(alpha x[:, seg s] B_s) (mats [N_s, r])."""
+    _chk_bf16(x, "lora_down x")
+    _chk_bf16(t, "lora_down t")
+    M, K = x.shape
+    R = lora_R(r)
+    _req(t.shape[0] == M and t.shape[1] == len(mats) * R, f"lora_down: t must be [{M}, {len(mats) * R}]")
+    starts = None
+    for m in mats:
+        _req(tuple(m.shape[1:]) == ((r,) if sliced else (K,)) and (sliced or m.shape[0] == r),
+             f"lora_down: segment shape {tuple(m.shape)}")
+    if sliced:
+        st, tot = _starts([m.shape[0] for m in mats])
+        _req(tot == K, "lora_down: sliced segment rows must sum to x columns")
+        starts = st + [tot]
+    segs = _lora_segs(mats, r, starts)
+    L.check(L.lib().svla_lora_down(M, K, x.data_ptr(), _ld(x), ctypes.byref(segs),
+                                   L.LORA_SLICED if sliced else L.LORA_SHARED, alpha, t.data_ptr(), _ld(t), _stream()),
+            "svla_lora_down")
+
+
+def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: int, summed: bool = False,
+            alpha: float = 1.0, rope=None, geglu_h: Optional[torch.Tensor] = None):
+    """In place c = epi(bf16(c + bf16(alpha t S))): sliced (mats B_s [N_s, r], the forward) or summed (mats A_s
+    [r, N]: the input gradient and the merge).  rope = (cos, sin, L, D, rotated columns); geglu_h: the GeGLU output."""
+    _chk_bf16(c, "lora_up c")
+    _chk_bf16(t, "lora_up t")
+    M, N = c.shape
+    _req(t.shape[0] == M, "lora_up: t rows")
+    starts = None
+    if summed:
+        for m in mats:
+            _req(tuple(m.shape) == (r, N), f"lora_up: summed segment shape {tuple(m.shape)} != {(r, N)}")
+    else:
+        st, tot = _starts([m.shape[0] for m in mats])
+        _req(tot == N and all(m.shape[1] == r for m in mats), "lora_up: sliced segment rows must sum to c columns")
+        starts = st + [tot]
+    _req(t.shape[1] >= (len(mats) - 1) * lora_R(r) + r, "lora_up: t is narrower than the adapters' slices")
+    segs = _lora_segs(mats, r, starts)
+    e = L.LoraEpilogue()
+    e.kind = L.LORA_EPI_NONE
+    if rope is not None:
+        cos, sin, Lr, D, cols = rope
+        _req(cos.stride(1) == 1 and sin.stride() == cos.stride(), "rope tables must share a row-major layout")
+        _req(cos.shape[0] >= Lr and cos.shape[1] >= D // 2, "lora_up: rope tables smaller than [L, D/2]")
+        e.kind = L.LORA_EPI_ROPE
+        e.rope_cos, e.rope_sin, e.rope_ld = cos.data_ptr(), sin.data_ptr(), cos.stride(0)
+        e.rope_L, e.rope_D, e.rope_cols = int(Lr), int(D), int(cols)
+    elif geglu_h is not None:
+        _chk_bf16(geglu_h, "lora_up h")
+        _req(tuple(geglu_h.shape) == (M, N // 2), "lora_up: h must be [M, N/2]")
+        e.kind = L.LORA_EPI_GEGLU
+        e.h, e.ldh = geglu_h.data_ptr(), _ld(geglu_h)
+    L.check(L.lib().svla_lora_up(M, N, c.data_ptr(), _ld(c), t.data_ptr(), _ld(t), ctypes.byref(segs),
+                                 L.LORA_SUMMED if summed else L.LORA_SLICED, alpha, ctypes.byref(e), _stream()),
+            "svla_lora_up")
+
+
+_lora_ws: dict = {}
+
+
+def _lora_workspace(nbytes: int) -> torch.Tensor:
+    """The fp32 partial buffer of svla_lora_wgrad for the current (device, stream); grown on demand (the old one stays
+    referenced by the stream's queued work through torch's allocator ordering: same stream)."""
+    s = torch.cuda.current_stream()
+    key = (s.device.index, s.cuda_stream)
+    buf = _lora_ws.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _lora_ws[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=s.device)
+    return buf
+
+
+def lora_wgrad(y: torch.Tensor, t: torch.Tensor, outs: Sequence[torch.Tensor], r: int, sliced: bool = False,
+               alpha: float = 1.0, accumulate: bool = False):
+    """Adapter gradients reduced over rows: shared outs_s [r, W] = alpha t[:, slice s]^T y, or sliced outs_s [W_s, r] =
+    alpha y[:, seg s]^T t[:, slice s].  Outputs are dense and written in place."""
+    _chk_bf16(y, "lora_wgrad y")
+    _chk_bf16(t, "lora_wgrad t")
+    M, W = y.shape
+    _req(t.shape[0] == M and t.shape[1] == len(outs) * lora_R(r), "lora_wgrad: t must be [M, nseg R]")
+    starts = None
+    for o in outs:
+        _req(o.is_contiguous(), "lora_wgrad: outputs must be contiguous")
+    if sliced:
+        st, tot = _starts([o.shape[0] for o in outs])
+        _req(tot == W and all(o.shape[1] == r for o in outs), "lora_wgrad: sliced output rows must sum to y columns")
+        starts = st + [tot]
+    else:
+        for o in outs:
+            _req(tuple(o.shape) == (r, W), f"lora_wgrad: shared output shape {tuple(o.shape)} != {(r, W)}")
+    segs = _lora_segs(outs, r, starts)
+    mode = L.LORA_SLICED if sliced else L.LORA_SHARED
+    need = int(L.lib().svla_lora_wgrad_workspace_bytes(M, W, mode, len(outs), int(r)))
+    ws = _lora_workspace(need)
+    L.check(L.lib().svla_lora_wgrad(M, W, y.data_ptr(), _ld(y), t.data_ptr(), _ld(t), mode, ctypes.byref(segs), alpha,
+                                    1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()), "svla_lora_wgrad")
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]
 
 

@@ -103,6 +103,37 @@ class Gemma2RMSNorm(nn.Module):
         return f"{tuple(self.weight.shape)}, eps={self.eps}"
 
 
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+LORA_MERGE_MSG = "unmerged LoRA adapters: call merge_lora() first (the KV-cached kernels read the base weights only)"
+
+
+class LoRAAdapter(nn.Module):
+    """The LoRA pair of one nn.Linear (peft LoraLayer, reference train/spatialvla_finetune.py:262-300): y = W x +
+    scaling * B (A x), A [r, in], B [out, r], scaling = lora_alpha / r.  Attached as `<linear>.lora`, so the
+    parameters are `<linear>.lora.A` / `.lora.B` and the base state-dict keys stay as they are."""
+
+    def __init__(self, A: torch.Tensor, B: torch.Tensor, r: int, lora_alpha: float):
+        super().__init__()
+        self.A = nn.Parameter(A)
+        self.B = nn.Parameter(B)
+        self.r = int(r)
+        self.lora_alpha = float(lora_alpha)
+        self.scaling = float(lora_alpha) / int(r)
+
+    def extra_repr(self):
+        return f"r={self.r}, lora_alpha={self.lora_alpha}"
+
+
+def _lora_of(*linears):
+    """The adapters of these projections: () when none has one, else one per projection (all or none)."""
+    ads = [getattr(m, "lora", None) for m in linears]
+    if all(a is None for a in ads):
+        return ()
+    if any(a is None for a in ads):
+        raise RuntimeError("LoRA adapters must sit on all of q/k/v/o (or gate/up/down) of a layer together")
+    return ads
+
+
 class Gemma2MLP(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -118,6 +149,12 @@ class Gemma2MLP(nn.Module):
 
     def forward(self, x, mx_in=None, mx_dout=None):
         shp = x.shape
+        ads = _lora_of(self.gate_proj, self.up_proj, self.down_proj)
+        if ads:
+            ab = [p for a in ads for p in (a.A, a.B)]
+            out = Fn.GemmaMLPLoRAFn.apply(x.reshape(-1, shp[-1]), self.gate_proj.weight, self.up_proj.weight,
+                                          self.down_proj.weight, ads[0].scaling, ads[0].r, *ab)
+            return out.view(*shp[:-1], self.hidden_size)
         out = Fn.GemmaMLPFn.apply(x.reshape(-1, shp[-1]), self.gate_proj.weight, self.up_proj.weight,
                                   self.down_proj.weight, getattr(self, "_svla_fp8", None), mx_in, mx_dout)
         return out.view(*shp[:-1], self.hidden_size)
@@ -197,6 +234,9 @@ class Gemma2Attention(nn.Module):
         B, Lq, H = hidden_states.shape
         cfg = self.attn_cfg(B, Lq)
         cos, sin = rope
+        ads = _lora_of(self.q_proj, self.k_proj, self.v_proj, self.o_proj)
+        if ads and cache is not None:
+            raise RuntimeError(LORA_MERGE_MSG)
         if cache is not None:
             i = self.layer_idx
             out = Fn.gemma_attention_cached(hidden_states.reshape(B * Lq, H), self.q_proj.weight, self.k_proj.weight,
@@ -211,6 +251,14 @@ class Gemma2Attention(nn.Module):
             # sequence, which per-sequence tables ([B*L] rows, padded prompts) would not match
             raise NotImplementedError("per-sequence position_ids are an inference path (the reference's training "
                                       "positions are shared: modeling_spatialvla.py:367-372); run under no_grad")
+        if ads:
+            if attn_sink is not None:
+                raise NotImplementedError("output_attentions with unmerged LoRA adapters: call merge_lora() first")
+            ab = [p for a in ads for p in (a.A, a.B)]
+            out = Fn.GemmaAttentionLoRAFn.apply(hidden_states.reshape(B * Lq, H), self.q_proj.weight,
+                                                self.k_proj.weight, self.v_proj.weight, self.o_proj.weight, cos, sin,
+                                                attention_mask.kv_class, cfg, ads[0].scaling, ads[0].r, *ab)
+            return out.view(B, Lq, H)
         capture = {} if attn_sink is not None else None
         out = Fn.GemmaAttentionFn.apply(hidden_states.reshape(B * Lq, H), self.q_proj.weight, self.k_proj.weight,
                                         self.v_proj.weight, self.o_proj.weight, cos, sin, attention_mask.kv_class,
@@ -251,6 +299,8 @@ class Gemma2DecoderLayer(nn.Module):
         """BASELINE configs[4]: run the forward q|k|v, o, gate|up and down projections of this layer on the fp8
         MFMA GEMM (row-wise e4m3 activations and weights, fp32 accumulation); the backward stays bf16.  Training
         and the uncached forward only -- the KV-cached decode keeps the bf16 GEMV path."""
+        if enabled and getattr(self.self_attn.q_proj, "lora", None) is not None:
+            raise NotImplementedError("fp8 projections together with LoRA adapters are not built: merge_lora() first")
         f8 = Fn.FP8Weights() if enabled else None
         self.self_attn._svla_fp8 = f8
         self.mlp._svla_fp8 = f8
@@ -352,6 +402,8 @@ class Gemma2Model(nn.Module):
         input_layernorm (or the final norm) -- bitwise the reference order (:475-496, :777), two norm launches per
         layer instead of four."""
         layers = self.layers[: self.config.num_hidden_layers]
+        if any(getattr(l.self_attn.q_proj, "lora", None) is not None for l in layers):
+            raise RuntimeError(LORA_MERGE_MSG)
         pwait = getattr(self, "_svla_param_wait", None)
         if pwait is not None:
             for i in range(len(layers)):

@@ -32,7 +32,7 @@ ZOE_STREAM = [os.environ.get("SVLA_ZOE_STREAM", "1") != "0"]
 ZOE_STREAM_CAPTURE = [os.environ.get("SVLA_ZOE_STREAM_CAPTURE", "1") != "0"]
 from . import kernels as K
 from .configuration_spatialvla import SpatialVLAConfig
-from .modeling_gemma2 import Gemma2ForCausalLM, Gemma2KVCache, KVMask
+from .modeling_gemma2 import LORA_TARGETS, Gemma2ForCausalLM, Gemma2KVCache, KVMask, LoRAAdapter
 from .modeling_siglip import SiglipVisionModel
 
 SIGLIP_MEAN, SIGLIP_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
@@ -457,6 +457,9 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         dev = (input_ids if input_ids is not None else inputs_embeds).device
         if cache is None and use_cache and not torch.is_grad_enabled():
             cache = self.new_cache(B, Lq + 256)
+        if cache is not None:
+            self._require_merged("forward(past_key_values=...)" if past_key_values is not None
+                                 else "forward(use_cache=True) (it creates a KV cache)")
 
         image_features = None
         if pixel_values is not None:
@@ -593,6 +596,158 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         test_fp8_gpu.py; the captured prefill/decode graphs are dropped (the prefill changes)."""
         for layer in self.language_model.model.layers:
             layer.set_fp8_projections(enabled)
+        self.clear_decode_cache()
+
+    # ------------------------------------------------------------------ LoRA fine-tuning
+    def _lora_linears(self):
+        """[(module path, nn.Linear)] of the seven Gemma2 projections of every decoder layer, in layer order."""
+        out = []
+        for i, layer in enumerate(self.language_model.model.layers):
+            for sub, names in (("self_attn", LORA_TARGETS[:4]), ("mlp", LORA_TARGETS[4:])):
+                for n in names:
+                    out.append((f"language_model.model.layers.{i}.{sub}.{n}", getattr(getattr(layer, sub), n)))
+        return out
+
+    @property
+    def has_lora(self) -> bool:
+        return any(getattr(lin, "lora", None) is not None for _, lin in self._lora_linears())
+
+    def _require_merged(self, what: str):
+        if self.has_lora:
+            raise RuntimeError(f"{what}: call merge_lora() first (unmerged LoRA adapters; the KV-cached decode "
+                               "kernels read the base weights only)")
+
+    def add_lora(self, r: int, lora_alpha: float, target_modules="gemma2-linear", init: str = "gaussian",
+                 seed: Optional[int] = None):
+        """LoRA fine-tuning as the reference sets it up (train/spatialvla_finetune.py:262-302: LoraConfig(r,
+        lora_alpha, target_modules, init_lora_weights="gaussian"), dropout 0, get_peft_model): A [r, in] ~ N(0, 1/r^2)
+        (peft "gaussian": std 1/r) and B [out, r] = 0 in bf16 on every targeted nn.Linear, every other parameter
+        frozen.  Targets: the seven Gemma2 projections of every decoder layer ("gemma2-linear", or exactly those seven
+        names); the decoder layers then run Fn.GemmaAttentionLoRAFn / Fn.GemmaMLPLoRAFn.  Build the TrainEngine after
+        this call: its flat buffers then hold the adapters only."""
+        if not isinstance(r, int) or r % 8 != 0 or not 8 <= r <= 64:
+            raise ValueError(f"add_lora: r must be a multiple of 8 in [8, 64], got {r!r}")
+        if isinstance(target_modules, str):
+            if target_modules != "gemma2-linear":
+                raise NotImplementedError(f"add_lora: target_modules={target_modules!r}: only 'gemma2-linear' (q_proj, "
+                                          "k_proj, v_proj, o_proj, gate_proj, up_proj, down_proj of the Gemma2 decoder "
+                                          "layers) is built; SigLIP, projector, Ego3D, spatial_embed_tokens and "
+                                          "lm_head targets are not")
+            targets = set(LORA_TARGETS)
+        else:
+            targets = set(target_modules)
+        for t in sorted(targets - set(LORA_TARGETS)):
+            raise NotImplementedError(f"add_lora: target module {t!r} is not built (only {', '.join(LORA_TARGETS)} of "
+                                      "the Gemma2 decoder layers)")
+        if targets != set(LORA_TARGETS):
+            raise NotImplementedError("add_lora: the seven Gemma2 projections are adapted together; missing "
+                                      f"{sorted(set(LORA_TARGETS) - targets)}")
+        if init != "gaussian":
+            raise NotImplementedError(f"add_lora: init={init!r} (the reference uses init_lora_weights='gaussian')")
+        if self.has_lora:
+            raise RuntimeError("add_lora: adapters are already attached (merge_lora() first)")
+        if any(getattr(l.mlp, "_svla_fp8", None) is not None for l in self.language_model.model.layers):
+            raise NotImplementedError("add_lora: fp8 projections together with LoRA adapters are not built")
+        gen = torch.Generator(device="cpu")
+        if seed is not None:
+            gen.manual_seed(int(seed))
+        else:
+            gen.seed()
+        for p in self.parameters():
+            p.requires_grad_(False)
+        for _, lin in self._lora_linears():
+            w = lin.weight
+            A = (torch.randn(r, w.shape[1], generator=gen) / r).to(torch.bfloat16).to(w.device)
+            B = torch.zeros(w.shape[0], r, dtype=torch.bfloat16, device=w.device)
+            lin.lora = LoRAAdapter(A, B, r, lora_alpha)
+        self.clear_decode_cache()
+
+    @torch.no_grad()
+    def merge_lora(self):
+        """peft's merge_and_unload: W <- bf16(W + bf16(s B A)) on every adapted projection (svla_lora_up, summed mode,
+        C = W, T = B), then the adapters are removed and the decoder layers run their original Functions again.
+        Irreversible."""
+        if not self.has_lora:
+            raise RuntimeError("merge_lora: no adapters attached")
+        for _, lin in self._lora_linears():
+            ad = lin.lora
+            w = lin.weight.data
+            if w.dtype != torch.bfloat16 or not w.is_cuda:
+                raise RuntimeError("merge_lora runs on the GPU kernels: move the model to the GPU in bf16 first")
+            K.lora_up(w, ad.B.data, [ad.A.data], ad.r, summed=True, alpha=ad.scaling)
+            del lin.lora
+        Fn.WEIGHT_EPOCH[0] += 1
+        self.clear_decode_cache()
+
+    def save_lora(self, save_directory: str):
+        """The adapters in peft's on-disk layout: adapter_model.safetensors with keys
+        base_model.model.<module path>.lora_A.weight / .lora_B.weight and adapter_config.json."""
+        import json
+        from safetensors.torch import save_file
+        if not self.has_lora:
+            raise RuntimeError("save_lora: no adapters attached")
+        os.makedirs(save_directory, exist_ok=True)
+        tensors, ad = {}, None
+        for path, lin in self._lora_linears():
+            ad = lin.lora
+            tensors[f"base_model.model.{path}.lora_A.weight"] = ad.A.detach().to("cpu").contiguous()
+            tensors[f"base_model.model.{path}.lora_B.weight"] = ad.B.detach().to("cpu").contiguous()
+        save_file(tensors, os.path.join(save_directory, "adapter_model.safetensors"), metadata={"format": "pt"})
+        cfg = {"peft_type": "LORA", "r": ad.r, "lora_alpha": ad.lora_alpha, "target_modules": list(LORA_TARGETS),
+               "init_lora_weights": "gaussian", "lora_dropout": 0.0, "bias": "none", "fan_in_fan_out": False,
+               "modules_to_save": None, "inference_mode": True, "task_type": None}
+        with open(os.path.join(save_directory, "adapter_config.json"), "w") as f:
+            json.dump(cfg, f, indent=2, sort_keys=True)
+
+    def load_lora(self, load_directory: str):
+        """Attach the adapters of a save_lora() / peft directory.  Raises, listing the keys, if the file holds
+        adapters for modules outside the seven Gemma2 projections or ranks that differ between modules."""
+        import json
+        import re
+        from safetensors.torch import load_file
+        with open(os.path.join(load_directory, "adapter_config.json")) as f:
+            cfg = json.load(f)
+        if cfg.get("peft_type", "LORA") != "LORA":
+            raise NotImplementedError(f"load_lora: peft_type {cfg.get('peft_type')!r}")
+        if cfg.get("modules_to_save"):
+            raise NotImplementedError(f"load_lora: modules_to_save={cfg['modules_to_save']!r} is not built")
+        if float(cfg.get("lora_dropout") or 0.0) != 0.0:
+            raise NotImplementedError("load_lora: lora_dropout != 0 is not built")
+        tensors = load_file(os.path.join(load_directory, "adapter_model.safetensors"))
+        mine = dict(self._lora_linears())
+        found, foreign = {}, []
+        for k, v in tensors.items():
+            m = re.match(r"^base_model\.model\.(.+)\.lora_([AB])(?:\.default)?\.weight$", k)
+            if m is None or m.group(1) not in mine:
+                foreign.append(k)
+                continue
+            found.setdefault(m.group(1), {})[m.group(2)] = v
+        if foreign:
+            raise ValueError("load_lora: adapters for modules outside the Gemma2 q/k/v/o/gate/up/down projections (or "
+                             f"unknown keys) are not built: {sorted(foreign)}")
+        missing = [p for p in mine if set(found.get(p, {})) != {"A", "B"}]
+        if missing:
+            raise ValueError(f"load_lora: no complete adapter for {missing}")
+        ranks = {p: int(ab["A"].shape[0]) for p, ab in found.items()}
+        if len(set(ranks.values())) != 1:
+            raise ValueError("load_lora: ranks differ between modules: "
+                             f"{ {k + '.lora_A.weight': r for k, r in sorted(ranks.items())} }")
+        r = next(iter(ranks.values()))
+        for p, lin in mine.items():
+            a, b = found[p]["A"], found[p]["B"]
+            if tuple(a.shape) != (r, lin.weight.shape[1]) or tuple(b.shape) != (lin.weight.shape[0], r):
+                raise ValueError(f"load_lora: {p}: shapes {tuple(a.shape)} / {tuple(b.shape)} do not fit the projection")
+        if not self.has_lora:
+            self.add_lora(r, cfg.get("lora_alpha", r), seed=0)
+        with torch.no_grad():
+            for p, lin in mine.items():
+                ad = lin.lora
+                if ad.r != r:
+                    raise ValueError(f"load_lora: attached adapters have rank {ad.r}, the file has {r}")
+                ad.lora_alpha = float(cfg.get("lora_alpha", r))
+                ad.scaling = ad.lora_alpha / r
+                ad.A.copy_(found[p]["A"].to(ad.A.dtype))
+                ad.B.copy_(found[p]["B"].to(ad.B.dtype))
         self.clear_decode_cache()
 
     def clear_decode_cache(self):
@@ -757,6 +912,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         (:294) and fills the cache; decode: one token per step at position P+i+1 (:473-474), no pixel values
         after step 0 (:475-476), attending to the prompt and every earlier generated token.  Stops when every
         sequence has emitted eos or after max_new_tokens."""
+        self._require_merged("predict_action")
         self._wait_all_params()
         ids, pv, intr, am, dev = self._predict_inputs(model_inputs)
         eos = eos_token_id if eos_token_id is not None else self.config.text_config.eos_token_id
@@ -856,6 +1012,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             kwargs.pop(k, None)
         if kwargs:
             raise TypeError(f"generate: unsupported arguments {sorted(kwargs)}")
+        self._require_merged("generate")
         self._wait_all_params()
         eos = eos_token_id if eos_token_id is not None else self.config.text_config.eos_token_id
         if isinstance(eos, (list, tuple)):

@@ -1,0 +1,80 @@
+"""ms/step of a SpatialVLA-4B train step (B = 32 by default) through TrainEngine: full fine-tune, LoRA r = 32 on the
+kernels of csrc/lora.hip with the adapter gradients on the main stream (SVLA_LORA_WGRAD_STREAM=0) and on the side
+stream (the default), and LoRA r = 32 on the unfused composition (SVLA_LORA_KERNELS=0's path) -- with the
+flat-buffer and optimizer-state bytes of each.  The model and batches are bench.py's (same random init, same
+synthetic OXE batches)."""
+import argparse
+import gc
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+import bench
+from spatialvla_amd import functional as Fn, presets
+from spatialvla_amd.engine import TrainEngine
+
+
+def run(name, cfgd, args, lora, kernels, side=False):
+    dev = torch.device("cuda", 0)
+    saved = (Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0])
+    model = bench.build_model(cfgd, dev)
+    if lora:
+        model.add_lora(args.rank, float(args.rank), seed=0)
+    Fn.LORA_KERNELS[0] = kernels
+    Fn.LORA_WGRAD_STREAM[0] = side
+    total = args.warmup + args.steps
+    eng = TrainEngine(model, lr=2e-5, weight_decay=0.0, max_grad_norm=1.0, warmup_ratio=0.005,
+                      total_steps=max(total, 10), defer_host_checks=True)
+    batches = [bench.make_batch(cfgd, args.batch, 1 + s, dev) for s in range(total)]
+    for s in range(args.warmup):
+        eng.train_step(batches[s])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loss = None
+    for s in range(args.steps):
+        loss = eng.train_step(batches[args.warmup + s])
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / args.steps * 1e3
+    flat = eng.flat_param.numel() * 2 + eng.flat_grad.numel() * 2
+    opt = (eng.master.numel() + eng.m.numel() + eng.v.numel()) * 4
+    print(f"{name:24s} {ms:8.2f} ms/step  loss {float(loss):.4f}  trainable {len(eng.params)} tensors "
+          f"{eng.numel / 1e6:9.2f} M elems  flat param+grad {flat / 2**20:9.1f} MiB  optimizer state "
+          f"{opt / 2**20:9.1f} MiB  peak alloc {torch.cuda.max_memory_allocated() / 2**30:6.1f} GiB", flush=True)
+    Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0] = saved
+    del eng, model, batches
+    gc.collect()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    return ms
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="spatialvla_4b", choices=["spatialvla_4b", "tiny"])
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--rank", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=1,
+                    help="repeat the list of configurations this many times, alternating them; prints min / median / max")
+    ap.add_argument("--only", default="", help="comma list of: full, lora, lora-sidestream, lora-composed")
+    a = ap.parse_args()
+    import json
+    cfgd = json.loads(json.dumps(getattr(presets, a.config)()))
+    only = set(a.only.split(",")) if a.only else None
+    cfgs = [c for c in (("full", False, True, False), ("lora", True, True, False),
+                        ("lora-sidestream", True, True, True), ("lora-composed", True, False, False))
+            if only is None or c[0] in only]
+    times = {c[0]: [] for c in cfgs}
+    for rnd in range(a.rounds):
+        for name, lora, kern, side in cfgs:
+            times[name].append(run(f"{name} (r={a.rank})" if lora else name, cfgd, a, lora, kern, side))
+    if a.rounds > 1:
+        for name, v in times.items():
+            v = sorted(v)
+            print(f"{name:24s} over {len(v)} alternating rounds: min {v[0]:.2f}  median {v[len(v) // 2]:.2f}  "
+                  f"max {v[-1]:.2f} ms/step", flush=True)
