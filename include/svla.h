@@ -520,6 +520,15 @@ int svla_softcap_ce_rows(int64_t M, int64_t N, void* logits, int64_t ld, float c
 int svla_ce_finalize(int64_t M, int64_t N, int64_t ntiles, const float* row_stats, const void* logits, int64_t ldl,
                      const int64_t* target, float* lse, int64_t* argmax, float* loss_rows, float* loss_out,
                      void* stream);
+/* Row gather / scatter of bf16 matrices (the training step's lm_head runs over the rows that carry a label):
+ * gather: dst[i, :C] = src[rows[i], :C] for i < R (rows outside [0, M) give zeros);
+ * scatter: dst [M, C] in one pass: dst[rows[i], :C] = src[i, :C], every row not listed is zero-filled (a row listed
+ * twice takes its last entry; entries outside [0, M) are dropped).  rows: int64 [R] in any order; C, lds, ldd
+ * multiples of 8 elements, pointers 16-B aligned. */
+int svla_gather_rows_bf16(int64_t M, int64_t R, int64_t C, const int64_t* rows, const void* src, int64_t lds,
+                          void* dst, int64_t ldd, void* stream);
+int svla_scatter_rows_bf16(int64_t M, int64_t R, int64_t C, const int64_t* rows, const void* src, int64_t lds,
+                           void* dst, int64_t ldd, void* stream);
 /* dlogits[m, n] = scale*(softmax(y)[n] - [n==target]) * (1 - (y/cap)^2), y = bf16 logits; rows with
  * target < 0 get 0; columns in [N, ldd) zeroed.  scale = grad_loss / n_valid (device scalar). */
 int svla_ce_bwd(int64_t M, int64_t N, const void* logits, int64_t ldl, const float* lse, const int64_t* target,

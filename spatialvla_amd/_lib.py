@@ -164,6 +164,8 @@ SIGNATURES = {
     "svla_gelu_rows": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "svla_softcap_ce_rows": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "svla_ce_finalize": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "svla_gather_rows_bf16": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "svla_scatter_rows_bf16": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "svla_ce_bwd": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp]),
     "svla_conv2d_nhwc": (c_i32, [ctypes.POINTER(ConvArgs), c_vp]),
     "svla_action_accuracy": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_vp, c_vp,

@@ -832,6 +832,7 @@ __global__ __launch_bounds__(C::NTH, 1) void gemm_kernel(int64_t M, int64_t N, i
 #pragma unroll 1
     for (int kt = 0; kt < nk; ++kt) {
       vm_wait_upto<NLD, NST - 2>(min(NST - 2, nk - 1 - kt));
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of slot (kt - 1) % NST, refilled below
       __builtin_amdgcn_s_barrier();
       const int kn = kt + NST - 1;
       if (kn < nk) {

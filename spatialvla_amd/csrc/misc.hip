@@ -661,6 +661,55 @@ extern "C" int svla_add_bf16(int64_t n, const void* a, const void* b, void* out,
   return svla::check_launch("add");
 }
 
+// ------------------------------------------------------------------ row gather / scatter (lm_head over label rows)
+// one block per gathered row, 16-B vectors; rows outside [0, M) read as zeros
+__global__ __launch_bounds__(256) void gather_rows_kernel(int64_t M, int64_t C8, const int64_t* __restrict__ rows,
+                                                          const u32x4* __restrict__ src, int64_t lds8,
+                                                          u32x4* __restrict__ dst, int64_t ldd8) {
+  const int64_t i = blockIdx.x, m = rows[i];
+  const bool ok = m >= 0 && m < M;
+  for (int64_t c = threadIdx.x; c < C8; c += blockDim.x)
+    dst[i * ldd8 + c] = ok ? src[m * lds8 + c] : u32x4{0u, 0u, 0u, 0u};
+}
+
+// one block per destination row: the block looks its row up in the (short) row list, then copies the source row or
+// writes zeros -- the zero fill and the scatter as one pass over dst
+__global__ __launch_bounds__(256) void scatter_rows_kernel(int64_t R, int64_t C8, const int64_t* __restrict__ rows,
+                                                           const u32x4* __restrict__ src, int64_t lds8,
+                                                           u32x4* __restrict__ dst, int64_t ldd8) {
+  __shared__ int sidx;
+  const int64_t m = blockIdx.x;
+  if (threadIdx.x == 0) sidx = -1;
+  __syncthreads();
+  for (int64_t i = threadIdx.x; i < R; i += blockDim.x)
+    if (rows[i] == m) atomicMax(&sidx, (int)i);  // a repeated row: its last entry
+  __syncthreads();
+  const int i = sidx;
+  for (int64_t c = threadIdx.x; c < C8; c += blockDim.x)
+    dst[m * ldd8 + c] = i >= 0 ? src[(int64_t)i * lds8 + c] : u32x4{0u, 0u, 0u, 0u};
+}
+
+extern "C" int svla_gather_rows_bf16(int64_t M, int64_t R, int64_t C, const int64_t* rows, const void* src,
+                                     int64_t lds, void* dst, int64_t ldd, void* stream) {
+  SVLA_CHECK_ARG(M > 0 && R > 0 && R < ((int64_t)1 << 31) && C > 0 && rows && src && dst, "gather_rows: args");
+  SVLA_CHECK_ARG(C % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && lds >= C && ldd >= C && al16(src) && al16(dst),
+                 "gather_rows: C, ld multiples of 8 elements, 16-B aligned pointers");
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, M, C / 8, rows,
+                     (const u32x4*)src, lds / 8, (u32x4*)dst, ldd / 8);
+  return svla::check_launch("gather_rows");
+}
+
+extern "C" int svla_scatter_rows_bf16(int64_t M, int64_t R, int64_t C, const int64_t* rows, const void* src,
+                                      int64_t lds, void* dst, int64_t ldd, void* stream) {
+  SVLA_CHECK_ARG(M > 0 && M < ((int64_t)1 << 31) && R > 0 && R < ((int64_t)1 << 31) && C > 0 && rows && src && dst,
+                 "scatter_rows: args");
+  SVLA_CHECK_ARG(C % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && lds >= C && ldd >= C && al16(src) && al16(dst),
+                 "scatter_rows: C, ld multiples of 8 elements, 16-B aligned pointers");
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, R, C / 8, rows,
+                     (const u32x4*)src, lds / 8, (u32x4*)dst, ldd / 8);
+  return svla::check_launch("scatter_rows");
+}
+
 extern "C" int svla_ce_finalize(int64_t M, int64_t N, int64_t ntiles, const float* row_stats, const void* logits,
                                 int64_t ldl, const int64_t* target, float* lse, int64_t* argmax, float* loss_rows,
                                 float* loss_out, void* stream) {

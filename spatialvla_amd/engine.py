@@ -387,7 +387,12 @@ class TrainEngine:
         """forward + backward + ZeRO-1 exchange + clip + AdamW; returns the loss tensor (no host sync).
         A batch without pixel_values leaves the vision-side gradients unwritten: they are zeroed (an unused
         parameter's gradient is zero, as in the reference's DeepSpeed step), not left at the previous step's."""
-        out = self.model(**batch, return_dict=True)
+        # the step reads out.loss alone: the lm_head runs over the rows with a label (no logits output)
+        prev, self.model.head_label_rows = getattr(self.model, "head_label_rows", False), True
+        try:
+            out = self.model(**batch, return_dict=True)
+        finally:
+            self.model.head_label_rows = prev
         self.synchronize()  # overlap_optimizer: every AdamW done before the backward rewrites the gradients
         out.loss.backward()
         if batch.get("pixel_values") is None:

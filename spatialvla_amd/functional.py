@@ -1389,6 +1389,10 @@ class LMHeadCEFn(torch.autograd.Function):
         M = h.shape[0]
         V = w.shape[0]
         ldv = K.round_up(V, 64)
+        rows = stash.pop("label_rows", None) if stash is not None else None
+        if rows is not None:
+            return LMHeadCEFn._forward_rows(ctx, h, w, target, cap, stash, rows)
+        ctx.rows_only = False
         logits_buf = _empty(M, ldv, like=h)
         ntn = K.ceil_div(V, 128)
         stats = _empty(M, ntn, 3, dtype=F32, like=h)
@@ -1414,15 +1418,74 @@ class LMHeadCEFn(torch.autograd.Function):
         return logits_buf[:, :V], loss2[0]
 
     @staticmethod
+    def _forward_rows(ctx, h, w, target, cap, stash, rows):
+        """The training step's form (stash["label_rows"]: the R > 0 rows with a label, on the device, R known on the
+        host): the loss is a mean over those rows and its caller reads nothing else, so the projection, the softcap
+        pass and the statistics run over them alone -- the same plain-store GEMM over the gathered rows of h (each
+        row's logits bitwise those of the full product), R/M of the work and of the logits buffer.  No logits output
+        (None); argmax / lse keep their length M, -1 / NaN on the rows without a label.
+        The gather, the GEMM, the softcap pass and the statistics are libsvla kernels; the bookkeeping on length-R and
+        length-M vectors is torch (index_select of the targets, full + index_copy_ for argmax and lse: five launches
+        over at most M elements each)."""
+        M, V = h.shape[0], w.shape[0]
+        R = int(rows.numel())
+        ldv = K.round_up(V, 64)
+        h_r = _empty(R, h.shape[1], like=h)
+        K.gather_rows(rows, h, h_r)
+        t_r = target.index_select(0, rows)
+        logits_r = _empty(R, ldv, like=h)
+        ntn = K.ceil_div(V, 128)
+        stats = _empty(R, ntn, 3, dtype=F32, like=h)
+        K.linear_fwd(h_r, [w], logits_r[:, :V])
+        K.softcap_ce_rows(logits_r, V, stats, cap)
+        lse_r = _empty(R, dtype=F32, like=h)
+        argmax_r = _empty(R, dtype=torch.int64, like=h)
+        loss_rows = _empty(R, dtype=F32, like=h)
+        loss2 = _empty(2, dtype=F32, like=h)
+        K.ce_finalize(V, ntn, stats, logits_r[:, :V], t_r, lse_r, argmax_r, loss_rows, loss2)
+        stash["argmax"] = torch.full((M,), -1, dtype=torch.int64, device=h.device).index_copy_(0, rows, argmax_r)
+        stash["lse"] = torch.full((M,), float("nan"), dtype=F32, device=h.device).index_copy_(0, rows, lse_r)
+        stash["n_valid"] = loss2[1:2]
+        stash.pop("row_plan", None)
+        ctx.save_for_backward(h_r, w, logits_r, lse_r, t_r, loss2, rows)
+        ctx.cap, ctx.V, ctx.M = cap, V, M
+        ctx.rows_only = True
+        ctx.set_materialize_grads(False)
+        return None, loss2[0]
+
+    @staticmethod
+    def _backward_rows(ctx, dloss):
+        h_r, w, logits_r, lse_r, t_r, loss2, rows = ctx.saved_tensors
+        R, ldv = logits_r.shape
+        V = ctx.V
+        gscale = (dloss.float() / torch.clamp(loss2[1], min=1.0)).reshape(1).contiguous()
+        dw, acc, rw = _grad_dest(w, ctx.needs_input_grad[1])
+        dlog = _empty(R, ldv, like=h_r)
+        K.ce_bwd(V, logits_r[:, :V], lse_r, t_r, ctx.cap, gscale, dlog)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh_r = _empty(R, h_r.shape[1], like=h_r)
+            A = K._operand([dlog], L.LAYOUT_KC, k_valid=ldv)
+            Bop = K._operand([w], L.LAYOUT_RC, k_valid=V)
+            K.gemm(R, w.shape[1], ldv, A, Bop, [dh_r], [0], dh_r.stride(0), K._epi(L.EPI_STORE))
+            dh = _empty(ctx.M, h_r.shape[1], like=h_r)
+            K.scatter_rows(rows, dh_r, dh)
+        if dw is not None:
+            K.linear_wgrad(dlog[:, :V], h_r, [dw], accumulate=acc)
+        return dh, rw, None, None, None
+
+    @staticmethod
     def backward(ctx, dlogits_unused, dloss):
         """d(loss)/d(logits) is exactly zero on every row without a label (target < 0: the reference's
         CrossEntropyLoss ignore_index / attention-mask rows, modeling_spatialvla.py:415-430) -- at B=32 only the
         13 suffix rows of each 312-token episode carry one.  The softmax gradient and both lm_head backward GEMMs
         therefore run over the labelled rows only: dh is zero elsewhere and dW = sum over labelled rows, the same
         values as the dense products (whose other terms are exact zeros), at 1/24 of their cost."""
-        h, w, logits_buf, lse, target, loss2 = ctx.saved_tensors
         if dloss is None:  # the loss did not reach the graph's output
             return None, None, None, None, None
+        if ctx.rows_only:
+            return LMHeadCEFn._backward_rows(ctx, dloss)
+        h, w, logits_buf, lse, target, loss2 = ctx.saved_tensors
         M, ldv = logits_buf.shape
         V = ctx.V
         gscale = (dloss.float() / torch.clamp(loss2[1], min=1.0)).reshape(1).contiguous()

@@ -924,6 +924,31 @@ def ce_finalize(N, ntiles, row_stats, logits, target, lse, argmax, loss_rows, lo
                                      loss_out.data_ptr(), _stream()), "ce_finalize")
 
 
+def _rows_args(rows, src, dst, what):
+    _chk_bf16(src, what)
+    _chk_bf16(dst, what)
+    _req(rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.numel() > 0,
+         f"{what}: rows must be a non-empty contiguous int64 vector")
+    _req(src.dim() == 2 and dst.dim() == 2 and src.shape[1] == dst.shape[1] and src.stride(1) == 1
+         and dst.stride(1) == 1, f"{what}: src / dst must be 2-D with the same contiguous columns")
+
+
+def gather_rows(rows: torch.Tensor, src: torch.Tensor, dst: torch.Tensor):
+    """dst[i] = src[rows[i]] (bf16 [R, C] from [M, C]; svla_gather_rows_bf16)."""
+    _rows_args(rows, src, dst, "gather_rows")
+    _req(dst.shape[0] == rows.numel(), "gather_rows: dst needs one row per entry of rows")
+    L.check(L.lib().svla_gather_rows_bf16(src.shape[0], rows.numel(), src.shape[1], rows.data_ptr(), src.data_ptr(),
+                                          _ld(src), dst.data_ptr(), _ld(dst), _stream()), "gather_rows")
+
+
+def scatter_rows(rows: torch.Tensor, src: torch.Tensor, dst: torch.Tensor):
+    """dst[rows[i]] = src[i], every other row of dst zero, in one pass over dst (svla_scatter_rows_bf16)."""
+    _rows_args(rows, src, dst, "scatter_rows")
+    _req(src.shape[0] == rows.numel(), "scatter_rows: src needs one row per entry of rows")
+    L.check(L.lib().svla_scatter_rows_bf16(dst.shape[0], rows.numel(), src.shape[1], rows.data_ptr(), src.data_ptr(),
+                                           _ld(src), dst.data_ptr(), _ld(dst), _stream()), "scatter_rows")
+
+
 def ce_bwd(N, logits, lse, target, cap, grad_scale, dlogits):
     M = logits.shape[0]
     L.check(L.lib().svla_ce_bwd(M, N, logits.data_ptr(), _ld(logits), lse.data_ptr(), target.data_ptr(), cap,

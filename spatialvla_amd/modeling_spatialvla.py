@@ -175,6 +175,9 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         self.strict_checks = True
         self.defer_checks = False
         self._deferred = []
+        # True (TrainEngine.train_step sets it around its own forward): a forward with labels and gradients runs the
+        # lm_head over the rows that carry a label only and returns logits = None (LMHeadCEFn._forward_rows)
+        self.head_label_rows = False
         self.last_stash = {}
         self.post_init()
 
@@ -461,13 +464,19 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             self._require_merged("forward(past_key_values=...)" if past_key_values is not None
                                  else "forward(use_cache=True) (it creates a KV cache)")
 
-        image_features = None
-        if pixel_values is not None:
-            image_features = self.get_image_features(pixel_values, intrinsic)
-
         if labels is not None and input_ids is not None:  # reference :390-395 (BC path), sync-free
             has_pad = (labels == self.pad_token_id).any()
             labels = torch.where(has_pad & (input_ids == self.pad_token_id), -100, labels)
+        # the CE targets and the label-row plan depend on the batch alone: queued ahead of the vision tower, the
+        # plan's row count has long reached the host when the head (head_label_rows) or the backward asks for it
+        target = self._targets(labels, attention_mask, B, Lq, dev)
+        stash = {}
+        if labels is not None and torch.is_grad_enabled():
+            stash["row_plan"] = self._label_rows(target)
+
+        image_features = None
+        if pixel_values is not None:
+            image_features = self.get_image_features(pixel_values, intrinsic)
 
         if inputs_embeds is not None:
             hidden = self._merge_embeds(input_ids, inputs_embeds, image_features)
@@ -492,14 +501,19 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         h, all_h = self.language_model.model(hidden, mask, position_ids, output_hidden_states=bool(output_hidden_states),
                                              cache=cache, attn_sink=attn_sink)
 
-        target = self._targets(labels, attention_mask, B, Lq, dev)
-        stash = {}
-        if labels is not None and torch.is_grad_enabled():
-            stash["row_plan"] = self._label_rows(target)
+        if self.head_label_rows and "row_plan" in stash:
+            # the training step reads the loss alone: lm_head, softcap and statistics over the rows with a label
+            # (LMHeadCEFn._forward_rows); no label in the batch: the full path
+            order, cnt, ev = stash["row_plan"]
+            if ev is not None:
+                ev.synchronize()
+                cnt = int(cnt[0])
+            if cnt > 0:
+                stash["label_rows"] = order[:cnt]
         logits2d, loss = self.language_model.head(h, target, stash)
         self.last_stash = stash
-        logits = logits2d.view(B, Lq, -1)
-        if num_logits_to_keep:
+        logits = logits2d.view(B, Lq, -1) if logits2d is not None else None
+        if num_logits_to_keep and logits is not None:
             logits = logits[:, -num_logits_to_keep:]
         if labels is None:
             loss = None
