@@ -245,6 +245,40 @@ size_t svla_lora_wgrad_workspace_bytes(int64_t M, int64_t W, int32_t mode, int32
 int svla_lora_wgrad(int64_t M, int64_t W, const void* y, int64_t ldy, const void* t, int64_t ldt, int32_t mode,
                     const svla_lora_segs* outs, float alpha, int32_t accumulate, void* workspace, size_t ws_bytes,
                     void* stream);
+/* Decode-step (M <= 8 rows) projections with unmerged adapters (csrc/lora_decode.hip): the peft LoRA forward
+ * base(x) + lora_B(lora_A(x)) * s of train/spatialvla_finetune.py:262-300 on q/k/v/o and gate/up/down
+ * (model/modeling_gemma2.py:86-92, 351-354) for the KV-cached decode, the adapter term inside the GEMV that streams
+ * the base weights.  One wave per output row, fp32 accumulation in a fixed order, no atomics, no block waits for
+ * another, no allocation or host sync (graph-capturable).
+ *
+ * svla_lora_gemv_down: T[M, nseg R] = bf16(sum_k x[m,k] A_s[j,k]) for up to 3 adapters A_s [r][K] (segs, row stride
+ * segs->ld >= K) that share x[M, K] (ldx % 8 == 0, any K % 8 == 0); svla_lora_down's SHARED layout: R = round_up(r,
+ * 32), columns r..R-1 of every slice are written as zero.  norm != NULL (K <= 2560): x is an OUTPUT -- the norm pair
+ * of svla_gemv_rmsnorm2 runs in the prologue, h_out = bf16(res + bf16(rms(y; w1))), x = bf16(rms(h_out; w2)), both
+ * stored ([M][ld] / [M][ldx]) and bitwise svla_add_rmsnorm2_fwd, so the projection that follows needs no prologue. */
+typedef struct {
+  const void* res;           /* [M][ld] residual stream */
+  const void* y;             /* [M][ld] sublayer output */
+  const void* w1;            /* [K] weight of the norm applied to y */
+  const void* w2;            /* [K] weight of the norm applied to h_out */
+  void* h_out;               /* [M][ld] new residual stream */
+  int64_t ld;
+  float eps1, eps2;
+} svla_lora_norm2;
+int svla_lora_gemv_down(int64_t M, int64_t K, void* x, int64_t ldx, const svla_lora_norm2* norm,
+                        const svla_lora_segs* segs, void* t, int64_t ldt, void* stream);
+/* svla_lora_gemv: the base projection plus the adapter term in one pass over W [N][K] (a KC operand of up to 4 outer
+ * segments; GEGLU: gate | up, SVLA_SEG_GEGLU):
+ *   y[m,n] = bf16( bf16(sum_k x[m,k] W[n,k]) + bf16(scaling sum_j T[m, sR+j] B_s[n - start_s, j]) )
+ * with B_s [N_s][r] segmented by svla_lora_up's SLICED rules (bsegs: starts multiples of 16 from 0 to N, nseg <= 3)
+ * and T from svla_lora_gemv_down (ldt >= (nseg-1) R + r) -- the rounding points of a plain-store svla_gemm_bf16
+ * followed by svla_lora_up SLICED, so the cached decode and the uncached forward differ in fp32 summation order
+ * only; with B = 0 the output is the small-M GEMV's bits.  Epilogues (epi->kind): SVLA_EPI_STORE (c [M][N]);
+ * SVLA_EPI_GEGLU (N = 2 I, two segments of I rows): the adapted g and u go to epi->out1 / out2 and
+ * c [M][I] = bf16(bf16(gelu_tanh(g)) u), SVLA_EPI_GEGLU's element formula. */
+int svla_lora_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_operand* W, const void* t,
+                   int64_t ldt, const svla_lora_segs* bsegs, float scaling, void* c, int64_t ldc,
+                   const svla_epilogue* epi, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via

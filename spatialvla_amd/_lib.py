@@ -74,6 +74,11 @@ class LoraEpilogue(ctypes.Structure):
                 ("rope_sin", c_vp), ("rope_ld", c_i64), ("rope_cols", c_i64), ("h", c_vp), ("ldh", c_i64)]
 
 
+class LoraNorm2(ctypes.Structure):
+    _fields_ = [("res", c_vp), ("y", c_vp), ("w1", c_vp), ("w2", c_vp), ("h_out", c_vp), ("ld", c_i64),
+                ("eps1", c_f32), ("eps2", c_f32)]
+
+
 LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
 LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU = 0, 1, 2
 
@@ -106,6 +111,10 @@ SIGNATURES = {
     "svla_lora_wgrad_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "svla_lora_wgrad": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, ctypes.POINTER(LoraSegs), c_f32, c_i32,
                                 c_vp, ctypes.c_size_t, c_vp]),
+    "svla_lora_gemv_down": (c_i32, [c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(LoraNorm2), ctypes.POINTER(LoraSegs), c_vp,
+                                    c_i64, c_vp]),
+    "svla_lora_gemv": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(Operand), c_vp, c_i64,
+                               ctypes.POINTER(LoraSegs), c_f32, c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

@@ -656,15 +656,94 @@ DECODE_FUSED = [os.environ.get("SVLA_DECODE_FUSED", "1") != "0"]
 DECODE_NORM_FUSED = [os.environ.get("SVLA_DECODE_NORM_FUSED", "1") != "0"]
 
 
+# decode steps with unmerged LoRA adapters run each projection as svla_lora_gemv_down + svla_lora_gemv (9 launches per
+# layer); SVLA_LORA_DECODE_KERNELS=0 (and M > 8, or a shape those kernels refuse): the composition from the training
+# path's kernels (norm pair, then projection + lora_down + lora_up per projection: 15 launches) -- the A/B partner, the
+# second reference of the tests and the general fallback
+LORA_DECODE_KERNELS = [os.environ.get("SVLA_LORA_DECODE_KERNELS", "1") != "0"]
+
+
+def _lora_decode_ok(x_rows, k, weights, norm=False) -> bool:
+    return (LORA_DECODE_KERNELS[0] and all(w.stride(1) == 1 for w in weights)
+            and K.lora_gemv_ok(x_rows, k, [w.shape[0] for w in weights], norm))
+
+
+def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora):
+    """gemma_attention_cached with an adapter on each of q, k, v, o: lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv),
+    (Ao, Bo)).  Prefill: the uncached adapter forward's kernels (GemmaAttentionLoRAFn) with the RoPE + cache fill of
+    the base prefill; decode: the adapter GEMVs, or their composition."""
+    r, s, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo) = lora
+    ops = _lora_ops()
+    if pre is not None:
+        if p0 == 0:
+            raise ValueError("gemma_attention_cached: the fused norm prologue is a decode-step path (p0 > 0)")
+        M, H = pre[1].shape
+        like = pre[1]
+    else:
+        x = _c(x)
+        M, H = x.shape
+        like = x
+    B, Lq = cfg.B, cfg.L
+    qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
+    R = K.lora_R(r)
+    qkv = _empty(M, qd + 2 * kd, like=like)
+    attn = _empty(M, qd, like=like)
+    if cos.shape[0] != B * Lq:
+        cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
+    if p0 > 0 and _lora_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
+        t = _empty(M, 3 * R, like=like)
+        if pre is not None:  # the norm pair in the prologue of the rank-r GEMV, which also stores x for the projection
+            x = _empty(M, H, like=like)
+        K.lora_gemv_down(x, [Aq, Ak, Av], r, t, norm=pre)
+        K.lora_gemv(x, [wq, wk, wv], t, [Bq, Bk, Bv], r, s, qkv)
+    else:
+        if pre is not None:
+            x = _empty(M, H, like=like)
+            K.add_rmsnorm2_fwd(*pre, x)
+        t = ops.down(x, [Aq, Ak, Av], r)
+        K.linear_fwd(x, [wq, wk, wv], qkv)
+        ops.up(qkv, t, [Bq, Bk, Bv], r, s)
+    if p0 > 0:
+        if DECODE_FUSED[0]:
+            K.attn_decode_rope(qkv, Lq, cos, sin, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
+                               cfg.softcap, kv_class, cfg.window, attn)
+        else:
+            K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, p0)
+            K.attn_decode(qkv[:, :qd], Lq, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
+                          cfg.softcap, kv_class, cfg.window, attn)
+    else:
+        K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, 0, k_back=True)
+        lse = _empty(B, cfg.Hq, Lq, dtype=F32, like=like)
+        cls = kv_class[:, :Lq].contiguous()  # held until the launch: attn_args keeps only its pointer
+        a = K.attn_args(B, Lq, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
+                        qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, cls, cfg.window)
+        K.attn_fwd(a, attn, lse)
+    out = _empty(M, wo.shape[0], like=like)
+    if p0 > 0 and _lora_decode_ok(M, qd, [wo]):
+        t_o = _empty(M, R, like=like)
+        K.lora_gemv_down(attn, [Ao], r, t_o)
+        K.lora_gemv(attn, [wo], t_o, [Bo], r, s, out)
+    else:
+        t_o = ops.down(attn, [Ao], r)
+        K.linear_fwd(attn, [wo], out)
+        ops.up(out, t_o, [Bo], r, s)
+    return out
+
+
 @torch.no_grad()
 def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg: GemmaAttnCfg,
-                           pre=None, skip_o=False):
+                           pre=None, skip_o=False, lora=None):
     """Gemma2Attention.forward with a KV cache (modeling_gemma2.py:364-413, cache update :387-395), inference
     only.  x holds the cfg.L new tokens of each of the cfg.B sequences, at absolute positions p0 .. p0+L-1;
     their rotated k and v are written into rows p0.. of k_cache/v_cache ([B, capacity, Hkv*D]).  The prefill
     (p0 == 0) runs the flash kernel of the uncached forward over the prompt, so it is bit-identical to it;
     later steps run the decode kernel over the first p0+L cache rows.  pre = (res, y, w1, w2, eps1, eps2, h_out): a
-    decode step whose input x = rms(res + rms(y; w1); w2) is formed inside the q|k|v GEMV (h_out the new residual)."""
+    decode step whose input x = rms(res + rms(y; w1); w2) is formed inside the q|k|v GEMV (h_out the new residual).
+    lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections."""
+    if lora is not None:
+        # the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term needs T
+        # complete before the projection starts, which inside one launch would take a grid barrier
+        return _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora)
     if pre is not None:
         if p0 == 0:
             raise ValueError("gemma_attention_cached: the fused norm prologue is a decode-step path (p0 > 0)")
@@ -740,10 +819,35 @@ DECODE_MLP_PERSIST = [os.environ.get("SVLA_DECODE_MLP_PERSIST", "1") != "0"]
 
 
 @torch.no_grad()
-def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None):
+def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora=None):
     """Decode-step Gemma2 MLP (modeling_gemma2.py:91-92) whose input is the post-attention + pre-feedforward norm pair
     (:487-490), formed inside the gate|up GEMV: h_out = res + rms(y; w1) (the residual stream), returns
-    down(gelu_tanh(gate x) * up x) with x = rms(h_out; w2)."""
+    down(gelu_tanh(gate x) * up x) with x = rms(h_out; w2).
+    lora = (r, scaling, (Ag, Bg), (Au, Bu), (Ad, Bd)): unmerged adapters on the three projections."""
+    if lora is not None:
+        # With adapters neither the persistent svla_decode_mlp nor DECODE_O_FUSED is used: each adapter term needs T
+        # (a reduction over the whole input row) complete between the rank-r GEMV and the projection that adds it,
+        # which inside the persistent launch would mean a second grid barrier per projection; a launch boundary is
+        # the cheaper barrier (the persistent kernel's one barrier already costs what it saves on the o projection).
+        if o is not None:
+            raise ValueError("gemma_mlp_decode: the o projection inside the MLP launch is not built with adapters")
+        r, s, (Ag, Bg), (Au, Bu), (Ad, Bd) = lora
+        M, H = y.shape
+        I = wg.shape[0]
+        R = K.lora_R(r)
+        x = _empty(M, H, like=y)
+        if _lora_decode_ok(M, H, [wg, wu], norm=True) and _lora_decode_ok(M, I, [wd]):
+            t = _empty(M, 2 * R, like=y)
+            K.lora_gemv_down(x, [Ag, Au], r, t, norm=(res, y, w1, w2, eps1, eps2, h_out))
+            hact, g, u = (_empty(M, I, like=y) for _ in range(3))
+            K.lora_gemv(x, [wg, wu], t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
+            t_d = _empty(M, R, like=y)
+            K.lora_gemv_down(hact, [Ad], r, t_d)
+            out = _empty(M, wd.shape[0], like=y)
+            K.lora_gemv(hact, [wd], t_d, [Bd], r, s, out)
+            return out
+        K.add_rmsnorm2_fwd(res, y, w1, w2, eps1, eps2, h_out, x)
+        return GemmaMLPLoRAFn.apply(x, wg, wu, wd, s, r, Ag, Bg, Au, Bu, Ad, Bd)
     if o is not None:  # y = attn @ wo^T (the o projection), in the persistent launch or as its own GEMV
         attn, wo = o
         y = _empty(attn.shape[0], wo.shape[0], like=attn)

@@ -1080,6 +1080,77 @@ def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: i
             "svla_lora_up")
 
 
+LORA_GEMV_MAX_M = 8  # token rows of the decode-step adapter kernels (csrc/lora_decode.hip)
+
+
+def lora_gemv_ok(M: int, K: int, sizes: Sequence[int], norm: bool = False) -> bool:
+    """Whether svla_lora_gemv_down / svla_lora_gemv take this decode-step projection: M <= 8 rows, K % 8 == 0 (the norm
+    prologue: K <= GEMV_NORM_MAX_K), at most 3 adapters whose output slices start at multiples of 16."""
+    return (1 <= M <= LORA_GEMV_MAX_M and K % 8 == 0 and 1 <= len(sizes) <= 3 and _aligned(sizes, 16)
+            and sum(sizes) >= 16 and (not norm or K <= GEMV_NORM_MAX_K))
+
+
+def lora_gemv_down(x: torch.Tensor, mats: Sequence[torch.Tensor], r: int, t: torch.Tensor, norm=None):
+    """Decode step: t[M, nseg R] = bf16(x A_s^T) (mats [r, K], M <= 8; columns r..R-1 of a slice are zeroed).
+    norm = (res, y, w1, w2, eps1, eps2, h_out): x is an output -- h_out = bf16(res + rms(y; w1)), x = rms(h_out; w2)
+    (svla_add_rmsnorm2_fwd, bitwise) are formed in the prologue and stored (svla_lora_gemv_down)."""
+    _chk_bf16(x, "lora_gemv_down x")
+    _chk_bf16(t, "lora_gemv_down t")
+    M, K = x.shape
+    R = lora_R(r)
+    _req(t.shape[0] == M and t.shape[1] == len(mats) * R, f"lora_gemv_down: t must be [{M}, {len(mats) * R}]")
+    for m in mats:
+        _req(tuple(m.shape) == (r, K), f"lora_gemv_down: segment shape {tuple(m.shape)} != {(r, K)}")
+    segs = _lora_segs(mats, r)
+    nrm = None
+    if norm is not None:
+        res, y, w1, w2, eps1, eps2, h_out = norm
+        for a, nm in ((res, "res"), (y, "y"), (h_out, "h_out"), (w1, "w1"), (w2, "w2")):
+            _chk_bf16(a, "lora_gemv_down " + nm)
+        _req(res.shape == y.shape == h_out.shape == x.shape and _ld(res) == _ld(y) == _ld(h_out),
+             "lora_gemv_down: res/y/h_out rows")
+        _req(w1.numel() == K and w2.numel() == K, "lora_gemv_down: norm weights")
+        nrm = L.LoraNorm2()
+        nrm.res, nrm.y, nrm.w1, nrm.w2, nrm.h_out = (a.data_ptr() for a in (res, y, w1, w2, h_out))
+        nrm.ld, nrm.eps1, nrm.eps2 = _ld(y), float(eps1), float(eps2)
+    L.check(L.lib().svla_lora_gemv_down(M, K, x.data_ptr(), _ld(x), ctypes.byref(nrm) if nrm is not None else None,
+                                        ctypes.byref(segs), t.data_ptr(), _ld(t), _stream()), "svla_lora_gemv_down")
+
+
+def lora_gemv(x: torch.Tensor, weights: List[torch.Tensor], t: torch.Tensor, mats: Sequence[torch.Tensor], r: int,
+              scaling: float, out: torch.Tensor, geglu_out=None):
+    """Decode step: out = bf16(bf16(x cat(weights)^T) + bf16(scaling t_s B_s^T)) in one pass over the base weights
+    (mats B_s [N_s, r], one per weight, t from lora_gemv_down; M <= 8).  geglu_out = (g, u) with weights = [w_gate,
+    w_up]: the adapted g, u are stored there and out = bf16(gelu_tanh(g)) u (svla_lora_gemv)."""
+    for a, nm in ((x, "x"), (t, "t"), (out, "out")):
+        _chk_bf16(a, "lora_gemv " + nm)
+    M, K = x.shape
+    _req(len(weights) == len(mats), "lora_gemv: one B per weight")
+    sizes = [w.shape[0] for w in weights]
+    for w, b in zip(weights, mats):
+        _req(w.shape[1] == K and tuple(b.shape) == (w.shape[0], r), "lora_gemv: weight / B shapes")
+    st, N = _starts(sizes)
+    _req(t.shape[0] == M and t.shape[1] >= (len(mats) - 1) * lora_R(r) + r, "lora_gemv: t is narrower than the slices")
+    segs = _lora_segs(mats, r, st + [N])
+    if geglu_out is not None:
+        _req(len(weights) == 2 and sizes[0] == sizes[1], "lora_gemv: GEGLU takes [w_gate, w_up]")
+        for a in geglu_out:
+            _chk_bf16(a, "lora_gemv g/u")
+            _req(a.shape[0] >= M and a.shape[1] >= sizes[0], "lora_gemv: g/u shape")
+        _req(out.shape[0] >= M and out.shape[1] >= sizes[0], "lora_gemv: out shape")
+        W = _operand(weights, L.LAYOUT_KC, L.SEG_GEGLU, [0, sizes[0]])
+        e = _epi(L.EPI_GEGLU, out1=geglu_out[0], out2=geglu_out[1])
+    else:
+        _req(out.shape[0] >= M and out.shape[1] >= N, "lora_gemv: out shape")
+        ws = _merge_rows(list(weights))
+        wst, _ = _starts([w.shape[0] for w in ws])
+        W = _operand(ws, L.LAYOUT_KC, L.SEG_OUTER, wst)
+        e = _epi(L.EPI_STORE)
+    L.check(L.lib().svla_lora_gemv(M, N, K, x.data_ptr(), _ld(x), ctypes.byref(W), t.data_ptr(), _ld(t),
+                                   ctypes.byref(segs), float(scaling), out.data_ptr(), _ld(out), ctypes.byref(e),
+                                   _stream()), "svla_lora_gemv")
+
+
 _lora_ws: dict = {}
 
 

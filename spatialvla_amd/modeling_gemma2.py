@@ -134,6 +134,13 @@ def _lora_of(*linears):
     return ads
 
 
+def _lora_args(ads):
+    """The adapters of a sublayer as the KV-cached functions take them: (r, scaling, (A, B) per projection), or None."""
+    if not ads:
+        return None
+    return (ads[0].r, ads[0].scaling, *[(a.A.detach(), a.B.detach()) for a in ads])
+
+
 class Gemma2MLP(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -235,13 +242,14 @@ class Gemma2Attention(nn.Module):
         cfg = self.attn_cfg(B, Lq)
         cos, sin = rope
         ads = _lora_of(self.q_proj, self.k_proj, self.v_proj, self.o_proj)
-        if ads and cache is not None:
+        if ads and cache is not None and not getattr(self, "_svla_lora_decode", False):
             raise RuntimeError(LORA_MERGE_MSG)
         if cache is not None:
             i = self.layer_idx
             out = Fn.gemma_attention_cached(hidden_states.reshape(B * Lq, H), self.q_proj.weight, self.k_proj.weight,
                                             self.v_proj.weight, self.o_proj.weight, cos, sin, cache.key_cache[i],
-                                            cache.value_cache[i], cache.kv_class, cache.seen_tokens, cfg)
+                                            cache.value_cache[i], cache.kv_class, cache.seen_tokens, cfg,
+                                            lora=_lora_args(ads))
             return out.view(B, Lq, H)
         if cos.shape[0] != Lq and torch.is_grad_enabled() and (
                 hidden_states.requires_grad or any(w.requires_grad for w in (self.q_proj.weight, self.k_proj.weight,
@@ -345,6 +353,16 @@ class Gemma2Model(nn.Module):
         # reference :669 / :752-762: the training forward re-runs each decoder layer in the backward when set
         # (Gemma2ForCausalLM._set_gradient_checkpointing)
         self.gradient_checkpointing = False
+        # KV-cached forward with unmerged LoRA adapters (enable_lora_decode): off = refuse, as before the switch existed
+        self.lora_decode = False
+
+    def enable_lora_decode(self, enabled: bool = True):
+        """Let the KV-cached forward (prefill and decode steps) run with unmerged LoRA adapters attached: each adapted
+        projection of a decode step is svla_lora_gemv_down + svla_lora_gemv (Fn.gemma_attention_cached /
+        Fn.gemma_mlp_decode).  Off (the default): the cached forward refuses adapters (LORA_MERGE_MSG)."""
+        self.lora_decode = bool(enabled)
+        for layer in self.layers:
+            layer.self_attn._svla_lora_decode = self.lora_decode
 
     def get_input_embeddings(self):
         return self.embed_tokens
@@ -402,7 +420,7 @@ class Gemma2Model(nn.Module):
         input_layernorm (or the final norm) -- bitwise the reference order (:475-496, :777), two norm launches per
         layer instead of four."""
         layers = self.layers[: self.config.num_hidden_layers]
-        if any(getattr(l.self_attn.q_proj, "lora", None) is not None for l in layers):
+        if not self.lora_decode and any(getattr(l.self_attn.q_proj, "lora", None) is not None for l in layers):
             raise RuntimeError(LORA_MERGE_MSG)
         pwait = getattr(self, "_svla_param_wait", None)
         if pwait is not None:
@@ -448,16 +466,19 @@ class Gemma2Model(nn.Module):
                 po = layers[i - 1].post_feedforward_layernorm
                 res = torch.empty_like(h)
                 pre = (h, m, po.weight, layer.input_layernorm.weight, po.eps, layer.input_layernorm.eps, res)
-            fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0]  # o projection inside the MLP's launch
+            la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))
+            lm = _lora_args(_lora_of(mlp.gate_proj, mlp.up_proj, mlp.down_proj))
+            # o projection inside the MLP's launch (never with adapters: their term needs its own launch boundary)
+            fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None
             a = Fn.gemma_attention_cached(x if i == 0 else None, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight,
                                           at.o_proj.weight, cos, sin, cache.key_cache[i], cache.value_cache[i],
                                           cache.kv_class, cache.seen_tokens, at.attn_cfg(B, Lq), pre=pre,
-                                          skip_o=fuse_o)
+                                          skip_o=fuse_o, lora=la)
             pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
             h = torch.empty_like(res)
             m = Fn.gemma_mlp_decode(res, None if fuse_o else a, pa.weight, pf.weight, pa.eps, pf.eps, h,
                                     mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
-                                    o=(a, at.o_proj.weight) if fuse_o else None)
+                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm)
         po = layers[-1].post_feedforward_layernorm
         res, x = torch.empty_like(h), torch.empty_like(h)
         Kn.add_rmsnorm2_fwd(h, m, po.weight, self.norm.weight, po.eps, self.norm.eps, res, x)
@@ -489,6 +510,10 @@ class Gemma2ForCausalLM(nn.Module):
 
     def get_decoder(self):
         return self.model
+
+    def enable_lora_decode(self, enabled: bool = True):
+        """Gemma2Model.enable_lora_decode: the KV-cached forward with unmerged LoRA adapters (opt-in)."""
+        self.model.enable_lora_decode(enabled)
 
     def set_decoder(self, decoder):
         self.model = decoder

@@ -626,8 +626,30 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
     def has_lora(self) -> bool:
         return any(getattr(lin, "lora", None) is not None for _, lin in self._lora_linears())
 
+    @property
+    def lora_decode(self) -> bool:
+        return bool(self.language_model.model.lora_decode)
+
+    def enable_lora_decode(self, enabled: bool = True):
+        """Run predict_action, generate, forward(past_key_values=...) and forward(use_cache=True) with unmerged LoRA
+        adapters attached (mid-training evaluation, a base model with a swappable adapter from load_lora): the prefill
+        on the training forward's rank-r kernels, every decode-step projection as svla_lora_gemv_down + svla_lora_gemv
+        (9 launches per layer; DESIGN.md section 4 "LoRA").  Off (the default): those entry points refuse adapters and
+        ask for merge_lora().  The captured graphs read A and B in place, so an optimizer step on them needs no
+        re-capture; toggling the switch drops the decode states.  fp8 projections with adapters stay refused."""
+        self.language_model.enable_lora_decode(enabled)
+        self.clear_decode_cache()
+
+    def _adapter_key(self):
+        """What the captured decode graphs bake in about the adapters: the switch, the first adapter's storage, its
+        rank and scaling (None without adapters)."""
+        ad = getattr(self.language_model.model.layers[0].self_attn.q_proj, "lora", None)
+        if ad is None:
+            return None
+        return (self.lora_decode, ad.A.data_ptr(), ad.r, ad.scaling)
+
     def _require_merged(self, what: str):
-        if self.has_lora:
+        if self.has_lora and not self.lora_decode:
             raise RuntimeError(f"{what}: call merge_lora() first (unmerged LoRA adapters; the KV-cached decode "
                                "kernels read the base weights only)")
 
@@ -793,7 +815,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         # the graphs hold raw pointers: to the weights (rebound by TrainEngine) and, with fp8 projections, to the
         # e4m3 weight copies, which the next eager forward after an optimizer step (WEIGHT_EPOCH) frees and rebuilds
         fp8 = any(getattr(l.mlp, "_svla_fp8", None) is not None for l in self.language_model.model.layers)
-        wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1)
+        # ... and to the LoRA adapters (rebound by TrainEngine / load_lora), with the path the switch selects
+        wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1, self._adapter_key())
         if st is not None and st["wptr"] != wptr:  # weights were rebound since capture: the graphs are stale
             states.pop(key)
             st = None

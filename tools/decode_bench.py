@@ -31,6 +31,58 @@ def timed(fn, reps):
     return times[len(times) // 2], out
 
 
+def lora_main(args):
+    """--lora R: ms per decode token (and prefill + first token) of three variants in one process, three alternating
+    rounds: the adapters merged into the weights (the base path), unmerged on svla_lora_gemv_down / svla_lora_gemv
+    (enable_lora_decode), and unmerged composed from the training-path kernels (SVLA_LORA_DECODE_KERNELS=0).  One model
+    per variant, each warmed up (and its graphs captured) under its own setting, so the rounds only replay."""
+    from bench import build_model, make_batch
+    from spatialvla_amd import functional as Fn, presets
+    dev = torch.device("cuda:0")
+    cfgd = json.loads(json.dumps(presets.spatialvla_4b()))
+    b = make_batch(cfgd, args.batch, 4321, dev)
+    P = int((b["token_type_ids"][0] == 0).sum())
+    inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
+    n_long = args.new_tokens + args.long
+    models, toks = {}, {}
+    for name in args.variants.split(","):
+        m = build_model(cfgd, dev).eval()
+        m.add_lora(args.lora, float(args.lora), seed=1)
+        gen = torch.Generator(device="cpu").manual_seed(2)
+        with torch.no_grad():
+            for _, lin in m._lora_linears():  # a trained adapter: B away from its zero initialisation
+                lin.lora.B.copy_((torch.randn(lin.lora.B.shape, generator=gen) * 0.01).to(torch.bfloat16))
+        if name == "merged":
+            m.merge_lora()
+        else:
+            m.enable_lora_decode()
+        Fn.LORA_DECODE_KERNELS[0] = name != "adapters_composed"
+        with torch.no_grad():  # warm-up under the variant's setting: every graph this model replays is captured here
+            m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1)
+            toks[name] = m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1)
+        models[name] = m
+    Fn.LORA_DECODE_KERNELS[0] = True
+    rounds = []
+    with torch.no_grad():
+        for _ in range(args.rounds):
+            row = {}
+            for name, m in models.items():
+                t1, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1), args.reps)
+                tl, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1),
+                              max(3, args.reps // 2))
+                row[name] = {"ms_prefill_plus_first": round(t1, 2), "ms_per_decode_token": round((tl - t1) / (n_long - 1), 4)}
+            rounds.append(row)
+    per = {n: [r[n]["ms_per_decode_token"] for r in rounds] for n in models}
+    print(json.dumps({
+        "metric": "SpatialVLA-4B greedy decode latency with LoRA adapters", "unit": "ms", "batch": args.batch, "r": args.lora,
+        "prompt_tokens": P, "decode_tokens_timed": n_long - 1, "rounds": rounds,
+        "ms_per_decode_token_min_max": {n: [min(v), max(v)] for n, v in per.items()},
+        "kernels_tokens_equal_composed": (bool(torch.equal(toks["adapters_kernels"], toks["adapters_composed"]))
+                                          if "adapters_kernels" in toks and "adapters_composed" in toks else None),
+        "decode_graphs": bool(next(iter(models.values())).decode_graphs), "dtype": "bf16",
+        "data": "synthetic OXE-shaped prompt, random-init weights and adapters"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
@@ -38,7 +90,14 @@ def main():
     ap.add_argument("--long", type=int, default=36, help="extra tokens for the per-token slope")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-uncached", action="store_true")
+    ap.add_argument("--lora", type=int, default=0, metavar="R",
+                    help="rank-R adapters: merged vs unmerged (adapter GEMVs) vs unmerged (composed), three rounds")
+    ap.add_argument("--variants", default="merged,adapters_kernels,adapters_composed",
+                    help="--lora: which of merged, adapters_kernels, adapters_composed to run (a kernel trace takes one)")
+    ap.add_argument("--rounds", type=int, default=3, help="--lora: alternating rounds")
     args = ap.parse_args()
+    if args.lora:
+        return lora_main(args)
     from bench import build_model, make_batch
     from spatialvla_amd import presets
     dev = torch.device("cuda:0")
