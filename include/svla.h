@@ -211,6 +211,10 @@ typedef struct {
   int64_t rope_cols;
   void* h;                   /* GEGLU: second output [M][ldh], N/2 columns */
   int64_t ldh;
+  void* mx_q;                /* GEGLU only, else NULL: also the OCP MX e4m3 copy of h, written by the same pass -- the    */
+  int64_t mx_ldq;            /* fields of svla_epilogue: [M][mx_ldq] bytes, E8M0 scales in svla_quant_mx_rows' tile-major */
+  void* mx_scales;           /* layout (mx_sld >= 4 M), bitwise svla_quant_mx_rows of the stored bf16 h; N/2 % 128 == 0.  */
+  int64_t mx_sld;            /* g | u and h are the bits of the call without it                                           */
 } svla_lora_epilogue;
 /* T[M, nseg R] (bf16, row stride ldt >= nseg R) from X[M, K] (ldx % 8 == 0, K % 8 == 0), fp32 accumulation, any
  * M >= 1; columns r..R-1 of every slice are written as zero.  The peft lora_A product and its transpose in backward
@@ -230,7 +234,8 @@ int svla_lora_down(int64_t M, int64_t K, const void* x, int64_t ldx, const svla_
  * Epilogues: NONE; ROPE = the rotation of SVLA_EPI_ROPE / svla_qkv_rope_fill on columns < rope_cols (same tables,
  * row -> position rule and rounding points; rope_D % 32 == 0); GEGLU (SLICED, two segments of N/2 columns): C holds
  * g | u, both stay in place after the update and h = bf16(bf16(gelu_tanh(g)) u) goes to epi->h -- SVLA_EPI_GEGLU's
- * element formula, so svla_geglu_bwd recomputes the same bits. */
+ * element formula, so svla_geglu_bwd recomputes the same bits; with epi->mx_q set (N/2 % 128 == 0, else refused) the
+ * same pass also writes svla_quant_mx_rows(h), the fp8 down projection's operand, bit for bit. */
 int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const void* t, int64_t ldt, const svla_lora_segs* segs,
                  int32_t mode, float alpha, const svla_lora_epilogue* epi, void* stream);
 /* The adapter gradients (autograd of the peft LoRA layer, train/spatialvla_finetune.py:262-300), reduced over the M

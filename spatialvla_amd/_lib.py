@@ -71,7 +71,8 @@ class LoraSegs(ctypes.Structure):
 
 class LoraEpilogue(ctypes.Structure):
     _fields_ = [("kind", c_i32), ("rope_L", c_i32), ("rope_D", c_i32), ("_pad", c_i32), ("rope_cos", c_vp),
-                ("rope_sin", c_vp), ("rope_ld", c_i64), ("rope_cols", c_i64), ("h", c_vp), ("ldh", c_i64)]
+                ("rope_sin", c_vp), ("rope_ld", c_i64), ("rope_cols", c_i64), ("h", c_vp), ("ldh", c_i64),
+                ("mx_q", c_vp), ("mx_ldq", c_i64), ("mx_scales", c_vp), ("mx_sld", c_i64)]
 
 
 class LoraNorm2(ctypes.Structure):

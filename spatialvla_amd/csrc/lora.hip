@@ -390,6 +390,102 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
   }
 }
 
+// GEGLU with the OCP MX e4m3 copy of h (the fp8 down projection's operand) out of the same pass.  One wave = the 32
+// gate columns of one MX block and their 32 up columns, two 16-column MFMA tiles each.  The tiles' rows are assigned so
+// that a lane owns 8 consecutive columns of row m = l & 15: MFMA row i of tile t is column 8 (i >> 2) + 4 t + (i & 3),
+// so lane group g = l >> 4 holds columns 8 g .. + 3 from tile 0 and 8 g + 4 .. + 7 from tile 1 (a dot product does not
+// depend on where its column sits in a tile: g | u and h are the bits of lora_up_kernel).  The four lanes l & 15,
+// + 16, + 32, + 48 hold one row's block, so its maximum is two xor shuffles on the h values still in registers;
+// the e4m3 bytes leave as one 8-B store a lane, the E8M0 byte from the block's first lane (svla_quant_mx_rows' layout
+// and element formula, fp8.hip).  N/2 % 128 == 0: every wave of the grid has all its columns, only rows are ragged.
+__global__ __launch_bounds__(256) void lora_up_geglu_mx_kernel(int64_t M, int64_t N, bf16_t* __restrict__ C, int64_t ldc,
+                                                               const bf16_t* __restrict__ T, int64_t ldt, Segs S,
+                                                               float alpha, bf16_t* __restrict__ H, int64_t ldh,
+                                                               uint8_t* __restrict__ Q, int64_t ldq,
+                                                               uint8_t* __restrict__ SC, int64_t sld) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, mi = l & 15, g = l >> 4;
+  const int64_t I = N >> 1;
+  const int64_t n0 = ((int64_t)blockIdx.x * 4 + w) * 32;  // the wave's MX block: gate columns n0 .., up columns I + n0 ..
+  const int ksteps = S.R >> 5;
+  bf16x8 fa[2][2], fb[2][2];  // [tile][k-step]: rows of B_gate / B_up, loaded once
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl) {
+    const int64_t col = n0 + 8 * (mi >> 2) + 4 * tl + (mi & 3);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int j = 32 * q + 8 * g;
+      fa[tl][q] = ld8(S.p[0] + col * S.ld + j, j < S.r);
+      fb[tl][q] = ld8(S.p[1] + col * S.ld + j, j < S.r);
+    }
+  }
+  const int64_t nrb = (M + 15) / 16;
+  bf16x8 ta[2], tb[2], ta_n[2], tb_n[2];
+  u32x4 ca, cb, ca_n = {0u, 0u, 0u, 0u}, cb_n = {0u, 0u, 0u, 0u};
+  auto load_rows = [&](int64_t rb, bf16x8(&xa)[2], bf16x8(&xb)[2], u32x4& ya, u32x4& yb) {
+    const int64_t m = rb * 16 + mi;
+    const bool mok = m < M;
+    const bf16_t* tr = T + (mok ? m : 0) * ldt;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int j = 32 * q + 8 * g;
+      xa[q] = ld8(tr + j, mok && j < S.r);
+      xb[q] = ld8(tr + S.R + j, mok && j < S.r);
+    }
+    const bf16_t* cr = C + (mok ? m : 0) * ldc + n0 + 8 * g;
+    ya = u32x4{0u, 0u, 0u, 0u};
+    yb = u32x4{0u, 0u, 0u, 0u};
+    if (mok) {
+      ya = *reinterpret_cast<const u32x4*>(cr);
+      yb = *reinterpret_cast<const u32x4*>(cr + I);
+    }
+  };
+  int64_t rb = blockIdx.y;
+  if (rb < nrb) load_rows(rb, ta_n, tb_n, ca_n, cb_n);
+  for (; rb < nrb; rb += gridDim.y) {
+    ta[0] = ta_n[0]; ta[1] = ta_n[1];
+    tb[0] = tb_n[0]; tb[1] = tb_n[1];
+    ca = ca_n;
+    cb = cb_n;
+    if (rb + gridDim.y < nrb) load_rows(rb + gridDim.y, ta_n, tb_n, ca_n, cb_n);
+    f32x4 da[2], db[2];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) {
+      da[tl] = f32x4{0.f, 0.f, 0.f, 0.f};
+      db[tl] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        if (q >= ksteps) continue;
+        da[tl] = mfma(fa[tl][q], ta[q], da[tl]);
+        db[tl] = mfma(fb[tl][q], tb[q], db[tl]);
+      }
+    }
+    // rows >= M went in as zeros and stay finite zeros: their lanes take part in the shuffles and store nothing
+    const int64_t m = rb * 16 + mi;
+    const bool mok = m < M;
+    float a[8], b[8], h[8];
+    unpack8(ca, a);
+    unpack8(cb, b);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {  // lora_up_kernel's bf16 chain and GeGLU formula
+      a[i] = round_bf(a[i] + round_bf(alpha * da[i >> 2][i & 3]));
+      b[i] = round_bf(b[i] + round_bf(alpha * db[i >> 2][i & 3]));
+      h[i] = gelu_bf16(a[i]) * b[i];
+    }
+    const u32x4 hv = pack8(h);
+    unpack8(hv, h);  // the bf16 h this launch stores: what the MX copy is made from
+    uint32_t byte;
+    const u32x2 qv = mx_block8<16, 32>(h, byte);  // the block's lanes are l & 15, + 16, + 32, + 48
+    if (mok) {
+      bf16_t* cr = C + m * ldc + n0 + 8 * g;
+      *reinterpret_cast<u32x4*>(H + m * ldh + n0 + 8 * g) = hv;
+      *reinterpret_cast<u32x4*>(cr) = pack8(a);
+      *reinterpret_cast<u32x4*>(cr + I) = pack8(b);
+      *reinterpret_cast<u32x2*>(Q + m * ldq + n0 + 8 * g) = qv;
+      if (g == 0) SC[(n0 >> 7) * sld + m * 4 + ((n0 & 127) >> 5)] = (uint8_t)byte;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ lora_wgrad
 // Both adapter gradients reduce over the rows m, which is the strided index of both operands, so both fragments run
 // down columns: each k-block of 32 rows is read with coalesced 16-B row loads (the next one in flight during the
@@ -573,6 +669,12 @@ int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// byte ranges [a, a + na) and [b, b + nb) share a byte
+bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
 // checks shared by the three entry points; fills S (every pointer 16-B aligned: fragments are 16-B loads)
 int make_segs(const char* what, const svla_lora_segs* in, Segs& S, bool need_starts, int64_t extent, int64_t start_mult) {
   SVLA_CHECK_ARG(in != nullptr, "%s: segment list is NULL", what);
@@ -682,14 +784,34 @@ extern "C" int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const vo
     E.h = (bf16_t*)epi->h;
     E.ldh = epi->ldh;
     nunits = (N / 2 + 15) / 16;
+    if (epi->mx_q) {  // + the MX e4m3 copy of h: a wave takes a whole 32-column block
+      SVLA_CHECK_ARG(epi->mx_scales && (N / 2) % 128 == 0 && epi->mx_ldq >= N / 2 && epi->mx_ldq % 8 == 0 &&
+                         ((uintptr_t)epi->mx_q & 7) == 0 && ((uintptr_t)epi->mx_scales & 3) == 0 &&
+                         epi->mx_sld >= 4 * M && epi->mx_sld % 4 == 0,
+                     "lora_up: GEGLU MX copy of h: N/2 % 128 == 0, mx_ldq >= N/2 (8-B rows), mx_sld >= 4 M");
+      // the kernel's pointers are __restrict__: the copy and its scales may share no byte with g | u, h or each other
+      const int64_t cb = ((M - 1) * ldc + N) * 2, hb = ((M - 1) * epi->ldh + N / 2) * 2;
+      const int64_t qb = (M - 1) * epi->mx_ldq + N / 2, sb = (N / 256) * epi->mx_sld;
+      SVLA_CHECK_ARG(!overlaps(epi->mx_q, qb, c, cb) && !overlaps(epi->mx_q, qb, epi->h, hb) &&
+                         !overlaps(epi->mx_scales, sb, c, cb) && !overlaps(epi->mx_scales, sb, epi->h, hb) &&
+                         !overlaps(epi->mx_q, qb, epi->mx_scales, sb),
+                     "lora_up: mx_q / mx_scales overlap c, h or each other");
+      nunits = N / 64;
+    }
   } else {
     SVLA_CHECK_ARG(kind == SVLA_LORA_EPI_NONE, "lora_up: unknown epilogue %d", kind);
   }
+  SVLA_CHECK_ARG(kind == SVLA_LORA_EPI_GEGLU || !epi || !epi->mx_q, "lora_up: the MX copy (epi->mx_q) is a GEGLU output");
   hipStream_t s = (hipStream_t)stream;
   const int64_t gx = (nunits + 3) / 4, nrb = (M + 15) / 16;
   int64_t gy = (8 * (int64_t)svla::num_cus() + gx - 1) / gx;
   gy = gy < 1 ? 1 : (gy > nrb ? nrb : gy);
   const dim3 grid((unsigned)gx, (unsigned)gy), block(256);
+  if (kind == SVLA_LORA_EPI_GEGLU && epi->mx_q) {
+    hipLaunchKernelGGL(lora_up_geglu_mx_kernel, grid, block, 0, s, M, N, (bf16_t*)c, ldc, (const bf16_t*)t, ldt, S, alpha,
+                       E.h, E.ldh, (uint8_t*)epi->mx_q, epi->mx_ldq, (uint8_t*)epi->mx_scales, epi->mx_sld);
+    return svla::check_launch("lora_up");
+  }
 #define SVLA_UP(SUMMED_, EPI_)                                                                                       \
   hipLaunchKernelGGL((lora_up_kernel<SUMMED_, EPI_>), grid, block, 0, s, M, N, (bf16_t*)c, ldc, (const bf16_t*)t, ldt, S, \
                      alpha, E, nunits)

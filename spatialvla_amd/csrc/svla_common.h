@@ -191,8 +191,11 @@ __device__ __forceinline__ int mx_exponent(float amax) {
 // (8 bytes), and the 4 E8M0 bytes of the 16-lane group gathered into the dword the group's first lane stores at sc4.
 // A NaN / +-Inf element makes its block NaN (scale 0xFF and e4m3 NaN elements).  Every lane of the 16-lane group must
 // call it (the shuffles); `ok` false: the lane stores nothing (its f must then be finite, e.g. zeros).
-__device__ __forceinline__ void mx_store8(float* f, bool ok, uint8_t* q8, uint8_t* sc4) {
-  const int lane = threadIdx.x & 63;
+// The element formula, once: the four lanes of a block are the xor-D1 / xor-D2 partners of one another (adjacent
+// lanes: 1, 2; csrc/lora.hip's GeGLU pass, whose block lanes are 16 apart: 16, 32); every one of them must call it.
+// Returns the 8 e4m3 bytes of this lane and, in `byte`, the block's E8M0 byte; f is overwritten.
+template <int D1, int D2>
+__device__ __forceinline__ u32x2 mx_block8(float* f, uint32_t& byte) {
   float amax = 0.f;
   int nonfinite = 0;
 #pragma unroll
@@ -200,18 +203,24 @@ __device__ __forceinline__ void mx_store8(float* f, bool ok, uint8_t* q8, uint8_
     amax = fmaxf(amax, fabsf(f[j]));
     nonfinite |= (__float_as_uint(f[j]) & 0x7f800000u) == 0x7f800000u;
   }
-  amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-  amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-  nonfinite |= __shfl_xor(nonfinite, 1, 64);
-  nonfinite |= __shfl_xor(nonfinite, 2, 64);
+  amax = fmaxf(amax, __shfl_xor(amax, D1, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, D2, 64));
+  nonfinite |= __shfl_xor(nonfinite, D1, 64);
+  nonfinite |= __shfl_xor(nonfinite, D2, 64);
   const int X = mx_exponent(amax);
   const float inv = __uint_as_float((uint32_t)(127 - X) << 23);  // 2^-X exactly (X >= -127 -> exponent <= 254)
 #pragma unroll
   for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] * inv, -448.f), 448.f);
   u32x2 qv = u32x2{cvt4(f[0], f[1], f[2], f[3]), cvt4(f[4], f[5], f[6], f[7])};
   if (nonfinite) qv = u32x2{0x7f7f7f7fu, 0x7f7f7f7fu};
+  byte = nonfinite ? 0xffu : (uint32_t)(127 + X);
+  return qv;
+}
+__device__ __forceinline__ void mx_store8(float* f, bool ok, uint8_t* q8, uint8_t* sc4) {
+  const int lane = threadIdx.x & 63;
+  uint32_t byte;
+  const u32x2 qv = mx_block8<1, 2>(f, byte);
   if (ok) *reinterpret_cast<u32x2*>(q8) = qv;
-  const uint32_t byte = nonfinite ? 0xffu : (uint32_t)(127 + X);
   uint32_t w = byte;
   w |= (uint32_t)__shfl_down((int)byte, 4, 16) << 8;
   w |= (uint32_t)__shfl_down((int)byte, 8, 16) << 16;

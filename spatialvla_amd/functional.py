@@ -447,11 +447,21 @@ class FP8Weights:
     gate|up [2I, H], down [H, I].  MX scaling: the forward copy W (MX blocks along the input dim K) and, for dgrad,
     W^T (blocks along the output dim N: the dgrad GEMM's reduction) each quantised from bf16 (svla_quant_mx_rows);
     row scaling: per-row fp32 scales, W^T the byte transpose of the forward copy.  Rebuilt lazily when a weight
-    moved, was modified in place, or the optimizer stepped (WEIGHT_EPOCH)."""
+    moved, was modified in place, or the optimizer stepped (WEIGHT_EPOCH).
+    frozen: the weights are the frozen base of LoRA adapters (enable_fp8_lora), which no optimizer step rewrites, so
+    the copies do not follow WEIGHT_EPOCH -- unless a weight sits in a TrainEngine's flat buffers (an engine built
+    while it was trainable steps it still); a move or an in-place change rebuilds them as always, and merge_lora()
+    drops the whole object."""
 
-    def __init__(self):
+    def __init__(self, frozen: bool = False):
         self._key = None
         self.mats = {}
+        self.frozen = frozen
+
+    def _epoch(self, mats):
+        if self.frozen and not any((m.data_ptr(), tuple(m.shape)) in _FLAT_PARAMS for m in mats):
+            return -1
+        return WEIGHT_EPOCH[0]
 
     @staticmethod
     def _rows(mats):
@@ -459,7 +469,7 @@ class FP8Weights:
         return mats[0] if len(mats) == 1 else torch.cat(mats, 0)
 
     def _entry(self, name, mats):
-        key = (WEIGHT_EPOCH[0], FP8_SCALING[0]) + tuple((m.data_ptr(), m._version) for m in mats)
+        key = (self._epoch(mats), FP8_SCALING[0]) + tuple((m.data_ptr(), m._version) for m in mats)
         hit = self.mats.get(name)
         if hit is None or hit["key"] != key:
             w = self._rows(mats)
@@ -998,8 +1008,8 @@ class _LoraKernelOps:
         return t
 
     @staticmethod
-    def up(c, t, Bs, r, s, rope=None, geglu_h=None):
-        K.lora_up(c, t, Bs, r, alpha=s, rope=rope, geglu_h=geglu_h)
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None):
+        K.lora_up(c, t, Bs, r, alpha=s, rope=rope, geglu_h=geglu_h, mx_out=mx_out)
 
     @staticmethod
     def down_t(dy, Bs, r, s):
@@ -1039,7 +1049,7 @@ class _LoraComposedOps:
         return t
 
     @staticmethod
-    def up(c, t, Bs, r, s, rope=None, geglu_h=None):
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None):
         R = K.lora_R(r)
         off = 0
         for i, b in enumerate(Bs):
@@ -1052,6 +1062,8 @@ class _LoraComposedOps:
         if geglu_h is not None:
             I = c.shape[1] // 2
             torch.mul(torch.nn.functional.gelu(c[:, :I], approximate="tanh"), c[:, I:], out=geglu_h)
+            if mx_out is not None:
+                K.quant_mx_rows(geglu_h, *mx_out)
 
     @staticmethod
     def down_t(dy, Bs, r, s):
@@ -1130,19 +1142,27 @@ def _frozen(ctx, idx, what):
 class GemmaAttentionLoRAFn(torch.autograd.Function):
     """GemmaAttentionFn with a LoRA adapter on each of q, k, v, o (reference train/spatialvla_finetune.py:262-300,
     peft Linear.forward: base(x) + lora_B(lora_A(x)) * scaling): the base q|k|v GEMM stores plainly, one rank-r pass
-    adds s t B^T and applies RoPE in place; the backward computes the adapter and input gradients only (frozen base)."""
+    adds s t B^T and applies RoPE in place; the backward computes the adapter and input gradients only (frozen base).
+    f8 (enable_fp8_lora): the base forward and input-gradient GEMMs of the sites in FP8_SITES run in e4m3 as in
+    GemmaAttentionFn (mx_in / mx_dout: the MX copies of x and dout from the norms); the rank-r products, the
+    attention and the adapter gradients read the bf16 tensors."""
 
     @staticmethod
     def forward(ctx, x, wq, wk, wv, wo, cos, sin, kv_class, cfg: GemmaAttnCfg, scaling: float, r: int,
-                Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo):
+                Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo, f8: Optional[FP8Weights] = None, mx_in: Optional[MXSlot] = None,
+                mx_dout: Optional[MXSlot] = None):
         _frozen(ctx, (1, 2, 3, 4), "GemmaAttentionLoRAFn")
         ops = _lora_ops()
         x = _c(x)
+        x_mx = mx_in.take(x) if mx_in is not None else None
         M = x.shape[0]
         qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
         t = ops.down(x, [Aq, Ak, Av], r)
         qkv = _empty(M, qd + 2 * kd, like=x)
-        K.linear_fwd(x, [wq, wk, wv], qkv)
+        if _fp8_site(f8, "qkv") is not None:
+            _fp8_linear(x, f8, "qkv", (wq, wk, wv), qkv, x_mx=x_mx)
+        else:
+            K.linear_fwd(x, [wq, wk, wv], qkv)
         ops.up(qkv, t, [Bq, Bk, Bv], r, scaling, rope=(cos, sin, cos.shape[0], cfg.D, qd + kd))
         attn = _empty(M, qd, like=x)
         lse = _empty(cfg.B, cfg.Hq, cfg.L, dtype=F32, like=x)
@@ -1151,11 +1171,15 @@ class GemmaAttentionLoRAFn(torch.autograd.Function):
         K.attn_fwd(a, attn, lse)
         t_o = ops.down(attn, [Ao], r)
         out = _empty(M, wo.shape[0], like=x)
-        K.linear_fwd(attn, [wo], out)
+        if _fp8_site(f8, "o") is not None:
+            _fp8_linear(attn, f8, "o", (wo,), out)
+        else:
+            K.linear_fwd(attn, [wo], out)
         ops.up(out, t_o, [Bo], r, scaling)
         ctx.save_for_backward(x, wq, wk, wv, wo, qkv, attn, lse, cos, sin, kv_class, t, t_o,
                               Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo)
         ctx.cfg, ctx.scaling, ctx.r = cfg, scaling, r
+        ctx.f8, ctx.mx_dout = f8, mx_dout
         return out
 
     @staticmethod
@@ -1172,7 +1196,11 @@ class GemmaAttentionLoRAFn(torch.autograd.Function):
         nig = ctx.needs_input_grad
         dt_o, g_o = _lora_grads(ops, dout, t_o, attn, r, s, [Bo], [Ao], nig[17:19])
         dattn = _empty(M, qd, like=x)
-        K.linear_dgrad(dout, [wo], dattn)
+        f8 = ctx.f8 if FP8_DGRAD[0] else None
+        if _fp8_site(f8, "o") is not None:
+            _fp8_dgrad(dout, f8, "o", (wo,), dattn, dy_mx=ctx.mx_dout.take(dout) if ctx.mx_dout is not None else None)
+        else:
+            K.linear_dgrad(dout, [wo], dattn)
         ops.up_t(dattn, dt_o, [Ao], r)
         dqkv = torch.empty_like(qkv)
         a = K.attn_args(cfg.B, cfg.L, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
@@ -1184,34 +1212,51 @@ class GemmaAttentionLoRAFn(torch.autograd.Function):
         dx = None
         if nig[0]:
             dx = torch.empty_like(x)
-            K.linear_dgrad(dqkv, [wq, wk, wv], dx)
+            if _fp8_site(f8, "qkv") is not None:
+                _fp8_dgrad(dqkv, f8, "qkv", (wq, wk, wv), dx)
+            else:
+                K.linear_dgrad(dqkv, [wq, wk, wv], dx)
             ops.up_t(dx, dt, [Aq, Ak, Av], r)
-        return (dx, None, None, None, None, None, None, None, None, None, None, *g_qkv, *g_o)
+        return (dx, None, None, None, None, None, None, None, None, None, None, *g_qkv, *g_o, None, None, None)
 
 
 class GemmaMLPLoRAFn(torch.autograd.Function):
     """GemmaMLPFn with a LoRA adapter on each of gate, up, down (reference train/spatialvla_finetune.py:262-300): the
     base gate|up GEMM stores g | u plainly into one [M, 2I] buffer, one rank-r pass adds the adapters and writes
-    h = gelu_tanh(g) u; the down adapter's gradient contribution enters dH before the GeGLU derivative pass."""
+    h = gelu_tanh(g) u; the down adapter's gradient contribution enters dH before the GeGLU derivative pass.
+    f8 (enable_fp8_lora): as GemmaAttentionLoRAFn; the rank-r GeGLU pass also writes the MX copy of h, the fp8 down
+    operand (svla_lora_epilogue.mx_q), and svla_geglu_bwd_mx that of [dg | du]."""
 
     @staticmethod
-    def forward(ctx, x, wg, wu, wd, scaling: float, r: int, Ag, Bg, Au, Bu, Ad, Bd):
+    def forward(ctx, x, wg, wu, wd, scaling: float, r: int, Ag, Bg, Au, Bu, Ad, Bd, f8: Optional[FP8Weights] = None,
+                mx_in: Optional[MXSlot] = None, mx_dout: Optional[MXSlot] = None):
         _frozen(ctx, (1, 2, 3), "GemmaMLPLoRAFn")
         ops = _lora_ops()
         x = _c(x)
+        x_mx = mx_in.take(x) if mx_in is not None else None
         M = x.shape[0]
         I = wg.shape[0]
         t = ops.down(x, [Ag, Au], r)
         gu = _empty(M, 2 * I, like=x)
-        K.linear_fwd(x, [wg, wu], gu)
+        if _fp8_site(f8, "gate_up") is not None:
+            _fp8_linear(x, f8, "gate_up", (wg, wu), gu, x_mx=x_mx)
+        else:
+            K.linear_fwd(x, [wg, wu], gu)
         h = _empty(M, I, like=x)
-        ops.up(gu, t, [Bg, Bu], r, scaling, geglu_h=h)
+        h_mx = None
+        if _fp8_site(f8, "down") is not None and FP8_SCALING[0] == "mx" and I % 128 == 0:
+            h_mx = (torch.empty(M, I, dtype=torch.float8_e4m3fn, device=x.device), K.MXScales(M, I, x.device))
+        ops.up(gu, t, [Bg, Bu], r, scaling, geglu_h=h, mx_out=h_mx)
         t_d = ops.down(h, [Ad], r)
         out = _empty(M, wd.shape[0], like=x)
-        K.linear_fwd(h, [wd], out)
+        if _fp8_site(f8, "down") is not None:
+            _fp8_linear(h, f8, "down", (wd,), out, x_mx=h_mx)
+        else:
+            K.linear_fwd(h, [wd], out)
         ops.up(out, t_d, [Bd], r, scaling)
         ctx.save_for_backward(x, wg, wu, wd, gu, h, t, t_d, Ag, Bg, Au, Bu, Ad, Bd)
         ctx.scaling, ctx.r = scaling, r
+        ctx.f8, ctx.mx_dout = f8, mx_dout
         return out
 
     @staticmethod
@@ -1225,16 +1270,29 @@ class GemmaMLPLoRAFn(torch.autograd.Function):
         nig = ctx.needs_input_grad
         dt_d, g_d = _lora_grads(ops, dout, t_d, h, r, s, [Bd], [Ad], nig[10:12])
         dgu = _empty(M, 2 * I, like=x)
-        K.linear_dgrad(dout, [wd], dgu[:, :I])
+        f8 = ctx.f8 if FP8_DGRAD[0] else None
+        if _fp8_site(f8, "down") is not None:
+            _fp8_dgrad(dout, f8, "down", (wd,), dgu[:, :I],
+                       dy_mx=ctx.mx_dout.take(dout) if ctx.mx_dout is not None else None)
+        else:
+            K.linear_dgrad(dout, [wd], dgu[:, :I])
         ops.up_t(dgu[:, :I], dt_d, [Ad], r)
-        K.geglu_bwd(dgu[:, :I], gu[:, :I], gu[:, I:], dgu[:, :I], dgu[:, I:])
+        f8gu = _fp8_site(f8, "gate_up")
+        dgu_mx = None
+        if f8gu is not None and FP8_SCALING[0] == "mx" and I % 128 == 0 and nig[0]:
+            dgu_mx = K.geglu_bwd_mx(dgu[:, :I], gu[:, :I], gu[:, I:], dgu[:, :I], dgu[:, I:])
+        else:
+            K.geglu_bwd(dgu[:, :I], gu[:, :I], gu[:, I:], dgu[:, :I], dgu[:, I:])
         dt, g_gu = _lora_grads(ops, dgu, t, x, r, s, [Bg, Bu], [Ag, Au], nig[6:10])
         dx = None
         if nig[0]:
             dx = torch.empty_like(x)
-            K.linear_dgrad(dgu, [wg, wu], dx)
+            if f8gu is not None:
+                _fp8_dgrad(dgu, f8, "gate_up", (wg, wu), dx, dy_mx=dgu_mx)
+            else:
+                K.linear_dgrad(dgu, [wg, wu], dx)
             ops.up_t(dx, dt, [Ag, Au], r)
-        return (dx, None, None, None, None, None, *g_gu, *g_d)
+        return (dx, None, None, None, None, None, *g_gu, *g_d, None, None, None)
 
 
 # ------------------------------------------------------------------------------------ SigLIP blocks

@@ -879,6 +879,9 @@ def im2col_patch(x, patch, cols):
 
 
 def affine(x, scale, offset, out):
+    # the first kernel of the model's forward: host tensors are refused here, before a launch would read host memory
+    _chk_bf16(x, "affine x")
+    _chk_bf16(out, "affine out")
     L.check(L.lib().svla_affine_bf16(x.numel(), x.data_ptr(), scale, offset, out.data_ptr(), _stream()), "affine")
 
 
@@ -1044,9 +1047,10 @@ def lora_down(x: torch.Tensor, mats: Sequence[torch.Tensor], r: int, t: torch.Te
 
 
 def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: int, summed: bool = False,
-            alpha: float = 1.0, rope=None, geglu_h: Optional[torch.Tensor] = None):
+            alpha: float = 1.0, rope=None, geglu_h: Optional[torch.Tensor] = None, mx_out=None):
     """In place c = epi(bf16(c + bf16(alpha t S))): sliced (mats B_s [N_s, r], the forward) or summed (mats A_s
-    [r, N]: the input gradient and the merge).  rope = (cos, sin, L, D, rotated columns); geglu_h: the GeGLU output."""
+    [r, N]: the input gradient and the merge).  rope = (cos, sin, L, D, rotated columns); geglu_h: the GeGLU output;
+    mx_out = (q [M, N/2] e4m3, MXScales): with geglu_h, the same pass also writes h's MX copy (N/2 % 128 == 0)."""
     _chk_bf16(c, "lora_up c")
     _chk_bf16(t, "lora_up t")
     M, N = c.shape
@@ -1075,6 +1079,11 @@ def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: i
         _req(tuple(geglu_h.shape) == (M, N // 2), "lora_up: h must be [M, N/2]")
         e.kind = L.LORA_EPI_GEGLU
         e.h, e.ldh = geglu_h.data_ptr(), _ld(geglu_h)
+    if mx_out is not None:  # the library checks the shapes (GEGLU only, N/2 % 128 == 0)
+        q, sc = mx_out
+        _req(q.dtype == FP8 and tuple(q.shape) == (M, N // 2) and q.stride(1) == 1 and sc.rows >= M
+             and sc.K == N // 2, "lora_up: mx_out must be (q [M, N/2] e4m3, MXScales of M rows and N/2 columns)")
+        e.mx_q, e.mx_ldq, e.mx_scales, e.mx_sld = q.data_ptr(), q.stride(0), sc.buf.data_ptr(), sc.ld
     L.check(L.lib().svla_lora_up(M, N, c.data_ptr(), _ld(c), t.data_ptr(), _ld(t), ctypes.byref(segs),
                                  L.LORA_SUMMED if summed else L.LORA_SLICED, alpha, ctypes.byref(e), _stream()),
             "svla_lora_up")

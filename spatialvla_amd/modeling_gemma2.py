@@ -154,13 +154,16 @@ class Gemma2MLP(nn.Module):
         if act not in ("gelu_pytorch_tanh", "gelu_tanh"):
             raise ValueError(f"Gemma2MLP: activation {act!r} not supported (kernel implements gelu_pytorch_tanh)")
 
-    def forward(self, x, mx_in=None, mx_dout=None):
+    def forward(self, x, mx_in=None, mx_dout=None, f8_lora=None):
+        """f8_lora: the layer's frozen FP8Weights (set_fp8_lora), handed in by the uncached layer forward only -- the
+        KV-cached loops call this module without it, so their prefill and decode steps stay bf16."""
         shp = x.shape
         ads = _lora_of(self.gate_proj, self.up_proj, self.down_proj)
         if ads:
             ab = [p for a in ads for p in (a.A, a.B)]
             out = Fn.GemmaMLPLoRAFn.apply(x.reshape(-1, shp[-1]), self.gate_proj.weight, self.up_proj.weight,
-                                          self.down_proj.weight, ads[0].scaling, ads[0].r, *ab)
+                                          self.down_proj.weight, ads[0].scaling, ads[0].r, *ab,
+                                          f8_lora, mx_in, mx_dout)
             return out.view(*shp[:-1], self.hidden_size)
         out = Fn.GemmaMLPFn.apply(x.reshape(-1, shp[-1]), self.gate_proj.weight, self.up_proj.weight,
                                   self.down_proj.weight, getattr(self, "_svla_fp8", None), mx_in, mx_dout)
@@ -237,7 +240,7 @@ class Gemma2Attention(nn.Module):
                                float(self.attn_logit_softcapping or 0.0), int(self.sliding_window or 0))
 
     def forward(self, hidden_states, attention_mask: KVMask, rope: tuple, cache: Optional[Gemma2KVCache] = None,
-                attn_sink: Optional[list] = None, mx_in=None, mx_dout=None):
+                attn_sink: Optional[list] = None, mx_in=None, mx_dout=None, f8_lora=None):
         B, Lq, H = hidden_states.shape
         cfg = self.attn_cfg(B, Lq)
         cos, sin = rope
@@ -265,7 +268,8 @@ class Gemma2Attention(nn.Module):
             ab = [p for a in ads for p in (a.A, a.B)]
             out = Fn.GemmaAttentionLoRAFn.apply(hidden_states.reshape(B * Lq, H), self.q_proj.weight,
                                                 self.k_proj.weight, self.v_proj.weight, self.o_proj.weight, cos, sin,
-                                                attention_mask.kv_class, cfg, ads[0].scaling, ads[0].r, *ab)
+                                                attention_mask.kv_class, cfg, ads[0].scaling, ads[0].r, *ab,
+                                                f8_lora, mx_in, mx_dout)
             return out.view(B, Lq, H)
         capture = {} if attn_sink is not None else None
         out = Fn.GemmaAttentionFn.apply(hidden_states.reshape(B * Lq, H), self.q_proj.weight, self.k_proj.weight,
@@ -308,10 +312,24 @@ class Gemma2DecoderLayer(nn.Module):
         MFMA GEMM (row-wise e4m3 activations and weights, fp32 accumulation); the backward stays bf16.  Training
         and the uncached forward only -- the KV-cached decode keeps the bf16 GEMV path."""
         if enabled and getattr(self.self_attn.q_proj, "lora", None) is not None:
-            raise NotImplementedError("fp8 projections together with LoRA adapters are not built: merge_lora() first")
+            raise NotImplementedError("fp8 projections of a layer with LoRA adapters go through set_fp8_lora() "
+                                      "(model.enable_fp8_lora()), or merge_lora() first")
         f8 = Fn.FP8Weights() if enabled else None
         self.self_attn._svla_fp8 = f8
         self.mlp._svla_fp8 = f8
+        if not enabled:
+            self.set_fp8_lora(False)
+
+    def set_fp8_lora(self, enabled: bool):
+        """The frozen base projections of this layer's LoRA-adapted sublayers on the fp8 GEMM (forward and input
+        gradient; Fn.GemmaAttentionLoRAFn / Fn.GemmaMLPLoRAFn), their e4m3 copies built once (FP8Weights(frozen)).
+        Only Gemma2DecoderLayer.forward without a cache reads the attribute and hands it to the sublayers: the
+        KV-cached forward (prefill and decode steps) never sees it and keeps its bf16 GEMM / GEMV / rank-r path."""
+        if enabled and getattr(self.self_attn.q_proj, "lora", None) is None:
+            raise RuntimeError("fp8 base projections under LoRA need adapters: add_lora() / load_lora() first")
+        f8 = Fn.FP8Weights(frozen=True) if enabled else None
+        self.self_attn._svla_fp8_lora = f8
+        self.mlp._svla_fp8_lora = f8
 
     def forward(self, hidden_states, attention_mask: KVMask, rope: tuple, cache: Optional[Gemma2KVCache] = None,
                 attn_sink: Optional[list] = None):
@@ -320,12 +338,15 @@ class Gemma2DecoderLayer(nn.Module):
         # gradients inside the pre-norm's backward kernel instead of an autograd add
         s1, s2 = Fn.ResidualSlot(), Fn.ResidualSlot()
         # fp8 projections (configs[4]): the norms also emit the MX e4m3 copies of q|k|v's and gate|up's inputs
-        f8 = getattr(self.self_attn, "_svla_fp8", None) if cache is None else None
+        f8 = f8l = None
+        if cache is None:
+            f8l = getattr(self.self_attn, "_svla_fp8_lora", None)  # frozen base under LoRA adapters (set_fp8_lora)
+            f8 = getattr(self.self_attn, "_svla_fp8", None) or f8l
         # (and the backward norms those of the o and down dgrad inputs)
         mx_a, mx_m = Fn.mx_slot_for(f8, "qkv"), Fn.mx_slot_for(f8, "gate_up")
         mx_da, mx_dm = Fn.mx_slot_for(f8, "o"), Fn.mx_slot_for(f8, "down")
         x = self.input_layernorm(hidden_states, s1, mx_a)
-        a = self.self_attn(x, attention_mask, rope, cache, attn_sink, mx_a, mx_da)
+        a = self.self_attn(x, attention_mask, rope, cache, attn_sink, mx_a, mx_da, f8l)
         pa, pf = self.post_attention_layernorm, self.pre_feedforward_layernorm
         if FUSED_NORM_PAIR[0]:
             # post-attention norm + residual and the pre-feedforward norm in one launch (AddRMSNorm2Fn); h's
@@ -337,7 +358,7 @@ class Gemma2DecoderLayer(nn.Module):
         else:
             h = pa.add_forward(hidden_states, a, s1, mx_da)
             x = pf(h, s2, mx_m)
-        m = self.mlp(x, mx_m, mx_dm)
+        m = self.mlp(x, mx_m, mx_dm, f8l)
         return self.post_feedforward_layernorm.add_forward(h, m, s2, mx_dm)
 
 

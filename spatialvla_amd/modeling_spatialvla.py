@@ -609,7 +609,27 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         row-scaled) MFMA GEMM, the attention and every backward GEMM unchanged (bf16).  Tolerances: tests/
         test_fp8_gpu.py; the captured prefill/decode graphs are dropped (the prefill changes)."""
         for layer in self.language_model.model.layers:
-            layer.set_fp8_projections(enabled)
+            layer.set_fp8_projections(enabled)  # off: also turns enable_fp8_lora off
+        self.clear_decode_cache()
+
+    @property
+    def fp8_lora(self) -> bool:
+        return any(getattr(l.mlp, "_svla_fp8_lora", None) is not None for l in self.language_model.model.layers)
+
+    def enable_fp8_lora(self, enabled: bool = True):
+        """With LoRA adapters attached: the frozen base q|k|v, o, gate|up and down projections of the training /
+        uncached forward on the MX fp8 GEMM, forward and input gradient (FP8_SITES / FP8_DGRAD as for
+        enable_fp8_projections); the rank-r adapter products, the attention and the adapter gradients stay bf16.  The
+        e4m3 copies (one W and one W^T per projection, beside the bf16 weights the decode and the merge read) are
+        built by the first forward and kept across optimizer steps, which rewrite the adapters only.  The KV-cached
+        forward (predict_action, generate, also under enable_lora_decode) stays on its bf16 path.  Turned off, and the
+        copies freed, by enable_fp8_lora(False), enable_fp8_projections(False) and merge_lora().  The captured decode
+        states are dropped."""
+        if enabled and not self.has_lora:
+            raise RuntimeError("enable_fp8_lora: no adapters attached (add_lora() / load_lora() first); a model "
+                               "without adapters runs its projections in fp8 through enable_fp8_projections()")
+        for layer in self.language_model.model.layers:
+            layer.set_fp8_lora(enabled)
         self.clear_decode_cache()
 
     # ------------------------------------------------------------------ LoRA fine-tuning
@@ -636,7 +656,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         on the training forward's rank-r kernels, every decode-step projection as svla_lora_gemv_down + svla_lora_gemv
         (9 launches per layer; DESIGN.md section 4 "LoRA").  Off (the default): those entry points refuse adapters and
         ask for merge_lora().  The captured graphs read A and B in place, so an optimizer step on them needs no
-        re-capture; toggling the switch drops the decode states.  fp8 projections with adapters stay refused."""
+        re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on."""
         self.language_model.enable_lora_decode(enabled)
         self.clear_decode_cache()
 
@@ -683,7 +703,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         if self.has_lora:
             raise RuntimeError("add_lora: adapters are already attached (merge_lora() first)")
         if any(getattr(l.mlp, "_svla_fp8", None) is not None for l in self.language_model.model.layers):
-            raise NotImplementedError("add_lora: fp8 projections together with LoRA adapters are not built")
+            raise NotImplementedError("add_lora: enable_fp8_projections() is on; attach the adapters to the bf16 "
+                                      "model, then enable_fp8_lora() runs the frozen base projections in fp8")
         gen = torch.Generator(device="cpu")
         if seed is not None:
             gen.manual_seed(int(seed))
@@ -705,6 +726,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         Irreversible."""
         if not self.has_lora:
             raise RuntimeError("merge_lora: no adapters attached")
+        self.enable_fp8_lora(False)  # the e4m3 copies are of the unmerged base weights: the merge reads bf16
         for _, lin in self._lora_linears():
             ad = lin.lora
             w = lin.weight.data

@@ -3,7 +3,8 @@ beside the unfused composition the same Functions run with SVLA_LORA_KERNELS=0 (
 elementwise ops) and beside the byte floor (bytes moved / 8 TB/s).  Each arm is captured into a graph of REPS calls
 and replayed (no host launch gaps); best of 3 interleaved rounds.  The operands of consecutive calls are the same
 buffers (46-370 MB), so part of them is served from the last-level cache: the fraction of the HBM byte floor printed
-here is an upper bound.  One line per (site, product)."""
+here is an upper bound.  One line per (site, product); for gate|up one more: the GeGLU pass that also writes the MX
+e4m3 copy of h (enable_fp8_lora) against the pass followed by svla_quant_mx_rows."""
 import os
 import sys
 
@@ -85,6 +86,18 @@ def bench_site(name, Kd, sizes, epi, r=R_):
         print(f"{name:8s} K={Kd:5d} N={N:5d} {prod:36s} kernel {ms['kernel'] * 1e3:8.1f} us  composed "
               f"{ms['composed'] * 1e3:8.1f} us  ({ms['composed'] / ms['kernel']:5.2f}x)  floor {floor * 1e3:6.1f} us "
               f"({100 * floor / ms['kernel']:5.1f} % of it)", flush=True)
+    if epi == "geglu":  # enable_fp8_lora: the MX e4m3 copy of h from the same pass, against the pass + svla_quant_mx_rows
+        h, I = kw["geglu_h"], N // 2
+        mx = (torch.empty(M, I, dtype=torch.float8_e4m3fn, device="cuda"), K.MXScales(M, I, "cuda"))
+        up = Fn._LoraKernelOps.up
+
+        def two_passes():
+            up(c, t, Bs, r, 1.0, **kw)
+            K.quant_mx_rows(h, *mx)
+        ms = _time({"fused": lambda: up(c, t, Bs, r, 1.0, mx_out=mx, **kw), "plain": lambda: up(c, t, Bs, r, 1.0, **kw),
+                    "two": two_passes})
+        print(f"{name:8s} K={Kd:5d} N={N:5d} up fwd (geglu) + MX copy of h: one pass {ms['fused'] * 1e3:8.1f} us  "
+              f"pass + quant_mx_rows {ms['two'] * 1e3:8.1f} us  pass without the copy {ms['plain'] * 1e3:8.1f} us", flush=True)
     return rows
 
 

@@ -1,7 +1,8 @@
 """ms/step of a SpatialVLA-4B train step (B = 32 by default) through TrainEngine: full fine-tune, LoRA r = 32 on the
 kernels of csrc/lora.hip with the adapter gradients on the main stream (SVLA_LORA_WGRAD_STREAM=0) and on the side
-stream (the default), and LoRA r = 32 on the unfused composition (SVLA_LORA_KERNELS=0's path) -- with the
-flat-buffer and optimizer-state bytes of each.  The model and batches are bench.py's (same random init, same
+stream (the default), LoRA r = 32 on the unfused composition (SVLA_LORA_KERNELS=0's path), and the side-stream LoRA
+step with the frozen base projections in fp8 (enable_fp8_lora) -- with the flat-buffer and optimizer-state bytes of
+each and, for the fp8 leg, the bytes of the e4m3 weight copies.  The model and batches are bench.py's (same random init, same
 synthetic OXE batches)."""
 import argparse
 import gc
@@ -18,12 +19,14 @@ from spatialvla_amd import functional as Fn, presets
 from spatialvla_amd.engine import TrainEngine
 
 
-def run(name, cfgd, args, lora, kernels, side=False):
+def run(name, cfgd, args, lora, kernels, side=False, fp8=False):
     dev = torch.device("cuda", 0)
     saved = (Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0])
     model = bench.build_model(cfgd, dev)
     if lora:
         model.add_lora(args.rank, float(args.rank), seed=0)
+    if fp8:
+        model.enable_fp8_lora()
     Fn.LORA_KERNELS[0] = kernels
     Fn.LORA_WGRAD_STREAM[0] = side
     total = args.warmup + args.steps
@@ -41,9 +44,17 @@ def run(name, cfgd, args, lora, kernels, side=False):
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     flat = eng.flat_param.numel() * 2 + eng.flat_grad.numel() * 2
     opt = (eng.master.numel() + eng.m.numel() + eng.v.numel()) * 4
+    copies = 0
+    for layer in model.language_model.model.layers:
+        f8 = getattr(layer.mlp, "_svla_fp8_lora", None)
+        for e in (f8.mats.values() if f8 is not None else ()):
+            if isinstance(e, dict):
+                copies += sum(e[k].numel() for k in ("q", "qt") if k in e)
+                copies += sum(e[k].buf.numel() for k in ("s", "st") if k in e and hasattr(e[k], "buf"))
     print(f"{name:24s} {ms:8.2f} ms/step  loss {float(loss):.4f}  trainable {len(eng.params)} tensors "
           f"{eng.numel / 1e6:9.2f} M elems  flat param+grad {flat / 2**20:9.1f} MiB  optimizer state "
-          f"{opt / 2**20:9.1f} MiB  peak alloc {torch.cuda.max_memory_allocated() / 2**30:6.1f} GiB", flush=True)
+          f"{opt / 2**20:9.1f} MiB  peak alloc {torch.cuda.max_memory_allocated() / 2**30:6.1f} GiB"
+          + (f"  e4m3 weight copies {copies / 2**20:7.1f} MiB" if fp8 else ""), flush=True)
     Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0] = saved
     del eng, model, batches
     gc.collect()
@@ -61,18 +72,19 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=1,
                     help="repeat the list of configurations this many times, alternating them; prints min / median / max")
-    ap.add_argument("--only", default="", help="comma list of: full, lora, lora-sidestream, lora-composed")
+    ap.add_argument("--only", default="", help="comma list of: full, lora, lora-sidestream, lora-composed, lora-fp8")
     a = ap.parse_args()
     import json
     cfgd = json.loads(json.dumps(getattr(presets, a.config)()))
     only = set(a.only.split(",")) if a.only else None
     cfgs = [c for c in (("full", False, True, False), ("lora", True, True, False),
-                        ("lora-sidestream", True, True, True), ("lora-composed", True, False, False))
+                        ("lora-sidestream", True, True, True), ("lora-composed", True, False, False),
+                        ("lora-fp8", True, True, True, True))
             if only is None or c[0] in only]
     times = {c[0]: [] for c in cfgs}
     for rnd in range(a.rounds):
-        for name, lora, kern, side in cfgs:
-            times[name].append(run(f"{name} (r={a.rank})" if lora else name, cfgd, a, lora, kern, side))
+        for name, lora, kern, side, *fp8 in cfgs:
+            times[name].append(run(f"{name} (r={a.rank})" if lora else name, cfgd, a, lora, kern, side, bool(fp8)))
     if a.rounds > 1:
         for name, v in times.items():
             v = sorted(v)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernel traces of the training step or the isolated Gemma2 block (what r6k_block_trace.sh / r6o_step_gaps.sh did):
-#   TAG=r8a tools/trace.sh step|block|lora
+#   TAG=r8a tools/trace.sh step|block|lora|lora-fp8
 # step:  rocprofv3 --kernel-trace --stats over bench.py (3 steps) -> gpurun_out/$TAG/${TAG}_step_breakdown.txt (+ gaps)
 # block: rocprofv3 --kernel-trace over tools/block_ab.py -> gpurun_out/$TAG/block_breakdown.txt
 set -o pipefail
@@ -25,5 +25,10 @@ case $1 in
       python3 tools/lora_step.py --only lora-sidestream --steps 2 --warmup 1 > "$O/lora_prof.log" 2>&1 || exit 1
     python tools/summarize_profile.py trace /tmp/prof_l "$O/$TAG" > "$O/trace_summary.log" 2>&1
     head -40 "$O/${TAG}_step_breakdown.txt" ;;
-  *) echo "usage: tools/trace.sh step|block|lora"; exit 2 ;;
+  lora-fp8)  # the same step with the frozen base projections in fp8 (enable_fp8_lora): quant_mx_* rows = what is re-quantised
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_lf -o trace --output-format csv -- \
+      python3 tools/lora_step.py --only lora-fp8 --steps 2 --warmup 1 > "$O/lora_prof.log" 2>&1 || exit 1
+    python tools/summarize_profile.py trace /tmp/prof_lf "$O/$TAG" > "$O/trace_summary.log" 2>&1
+    head -40 "$O/${TAG}_step_breakdown.txt" ;;
+  *) echo "usage: tools/trace.sh step|block|lora|lora-fp8"; exit 2 ;;
 esac
