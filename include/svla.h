@@ -182,17 +182,20 @@ int svla_gemm_fp8(int64_t M, int64_t N, int64_t K, const svla_operand* A, const 
                   const svla_epilogue* epi, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * LoRA adapters of the Gemma2 projections (csrc/lora.hip).  Replaces the peft LoRA layers the reference wraps its
+ * LoRA adapters of the Gemma2 projections and of the vision-side linears (csrc/lora.hip).  Replaces the peft LoRA layers the reference wraps its
  * linear modules in for fine-tuning -- train/spatialvla_finetune.py:262-300: LoraConfig(r, lora_alpha,
  * target_modules, init_lora_weights="gaussian"), get_peft_model -- whose forward is base(x) + lora_B(lora_A(x)) * s
- * with s = lora_alpha / r, for q/k/v/o and gate/up/down (model/modeling_gemma2.py:86-92, 351-354).
+ * with s = lora_alpha / r, for q/k/v/o and gate/up/down (model/modeling_gemma2.py:86-92, 351-354) and, with the
+ * reference's default lora_target="linear" (train/spatialvla_finetune.py:264-270), for the SigLIP q/k/v/out_proj/fc1/fc2
+ * (transformers siglip [3p]), the projector (model/modeling_spatialvla.py:124) and the Ego3D head (:59-64).
  * A "segment list" is up to 3 small bf16 matrices (one per adapter that shares the large matrix: q|k|v, gate|up), all
  * of rank r (a multiple of 8, 8..64) and row stride ld, 16-B aligned; each adapter's rank-space slice of T is
  * R = round_up(r, 32) columns wide: adapter s owns T[:, sR .. sR + r).  `start` (sliced modes): segment s covers
  * columns [start[s], start[s+1]) of the large matrix, start[0] = 0, start[nseg] = its width.
  * ---------------------------------------------------------------------------------------- */
 enum { SVLA_LORA_SHARED = 0, SVLA_LORA_SLICED = 1, SVLA_LORA_SUMMED = 2 };
-enum { SVLA_LORA_EPI_NONE = 0, SVLA_LORA_EPI_ROPE = 1, SVLA_LORA_EPI_GEGLU = 2 };
+enum { SVLA_LORA_EPI_NONE = 0, SVLA_LORA_EPI_ROPE = 1, SVLA_LORA_EPI_GEGLU = 2,
+       SVLA_LORA_EPI_GELU = 3, SVLA_LORA_EPI_RESID = 4, SVLA_LORA_EPI_SCALE = 5 };
 typedef struct {
   void* ptr[3];
   int64_t start[4];
@@ -204,13 +207,15 @@ typedef struct {
   int32_t kind;
   int32_t rope_L;            /* ROPE: as svla_epilogue (row m is position m % rope_L, heads of rope_D columns,        */
   int32_t rope_D;            /*       tables [rope_L][rope_D/2] bf16 with row stride rope_ld, columns < rope_cols)     */
-  int32_t _pad;
+  float post;                /* SCALE: the factor applied after the adapter term (the slot of the former padding word)     */
   const void* rope_cos;
   const void* rope_sin;
   int64_t rope_ld;
   int64_t rope_cols;
-  void* h;                   /* GEGLU: second output [M][ldh], N/2 columns */
+  void* h;                   /* GEGLU: second output [M][ldh], N/2 columns; GELU: [M][ldh], N columns */
   int64_t ldh;
+  const void* res;           /* RESID: bf16 [M][ldres] added after the adapter term (ldres % 8 == 0, >= N, 16-B aligned,  */
+  int64_t ldres;             /*        no byte shared with C)                                                             */
   void* mx_q;                /* GEGLU only, else NULL: also the OCP MX e4m3 copy of h, written by the same pass -- the    */
   int64_t mx_ldq;            /* fields of svla_epilogue: [M][mx_ldq] bytes, E8M0 scales in svla_quant_mx_rows' tile-major */
   void* mx_scales;           /* layout (mx_sld >= 4 M), bitwise svla_quant_mx_rows of the stored bf16 h; N/2 % 128 == 0.  */
@@ -235,7 +240,18 @@ int svla_lora_down(int64_t M, int64_t K, const void* x, int64_t ldx, const svla_
  * row -> position rule and rounding points; rope_D % 32 == 0); GEGLU (SLICED, two segments of N/2 columns): C holds
  * g | u, both stay in place after the update and h = bf16(bf16(gelu_tanh(g)) u) goes to epi->h -- SVLA_EPI_GEGLU's
  * element formula, so svla_geglu_bwd recomputes the same bits; with epi->mx_q set (N/2 % 128 == 0, else refused) the
- * same pass also writes svla_quant_mx_rows(h), the fp8 down projection's operand, bit for bit. */
+ * same pass also writes svla_quant_mx_rows(h), the fp8 down projection's operand, bit for bit.
+ * The vision-side linears (SLICED; each applies to v = bf16(C + bf16(alpha sum T S)), the value NONE stores):
+ *   GELU  (one segment; SigLIP fc1 + gelu_pytorch_tanh, transformers siglip [3p] SiglipMLP.forward): C keeps v, the
+ *         pre-activation svla_gelu_rows(mode 2) reads in backward, and epi->h[m][n] = bf16(gelu_tanh(v)) with
+ *         svla_gelu_rows(mode 0)'s element formula, bit for bit; h may share no byte with C;
+ *   RESID (SigLIP out_proj / fc2 + the encoder residual, transformers siglip [3p] SiglipEncoderLayer.forward; Ego3D
+ *         head.3 + the vision features, model/modeling_spatialvla.py:59-64, 327-328): C = bf16(v + res[m][n]) -- the
+ *         rounding points of SVLA_EPI_BIAS_RESID followed by a plain adapter add; res may share no byte with C;
+ *   SCALE (the projector and its / sqrt(hidden), model/modeling_spatialvla.py:124, 331-332): C = bf16(v * post), post
+ *         treated as SVLA_EPI_BIAS treats its alpha.
+ * Any N % 8 == 0: the last 16-column tile of an N with N % 32 == 16 (SigLIP's 4304) is handled.  Overlapping or
+ * misaligned h / res are refused (svla_last_error) before any launch. */
 int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const void* t, int64_t ldt, const svla_lora_segs* segs,
                  int32_t mode, float alpha, const svla_lora_epilogue* epi, void* stream);
 /* The adapter gradients (autograd of the peft LoRA layer, train/spatialvla_finetune.py:262-300), reduced over the M

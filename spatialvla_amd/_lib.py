@@ -70,8 +70,9 @@ class LoraSegs(ctypes.Structure):
 
 
 class LoraEpilogue(ctypes.Structure):
-    _fields_ = [("kind", c_i32), ("rope_L", c_i32), ("rope_D", c_i32), ("_pad", c_i32), ("rope_cos", c_vp),
+    _fields_ = [("kind", c_i32), ("rope_L", c_i32), ("rope_D", c_i32), ("post", c_f32), ("rope_cos", c_vp),
                 ("rope_sin", c_vp), ("rope_ld", c_i64), ("rope_cols", c_i64), ("h", c_vp), ("ldh", c_i64),
+                ("res", c_vp), ("ldres", c_i64),
                 ("mx_q", c_vp), ("mx_ldq", c_i64), ("mx_scales", c_vp), ("mx_sld", c_i64)]
 
 
@@ -81,7 +82,7 @@ class LoraNorm2(ctypes.Structure):
 
 
 LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
-LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU = 0, 1, 2
+LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU, LORA_EPI_GELU, LORA_EPI_RESID, LORA_EPI_SCALE = 0, 1, 2, 3, 4, 5
 
 # name -> (restype, argtypes); every entry point of include/svla.h
 SIGNATURES = {

@@ -223,7 +223,10 @@ __global__ __launch_bounds__(64 * DOWN_NW) void lora_down_kernel(int64_t M, int6
 // 16 at a time, the next row block's T and C loads issued before the current MFMAs.  C^T is accumulated (first
 // operand = the small matrix, column index on the rows), so a lane owns 4 consecutive columns of row m = l & 15 of
 // each tile: it reads them, adds, applies the epilogue and writes them back -- no element is touched by two lanes.
-enum { UP_NONE = 0, UP_ROPE = 1, UP_GEGLU = 2 };
+// GELU / RESID / SCALE (the vision-side linears: SigLIP fc1, out_proj | fc2 | Ego3D head.3, the projector) work on the
+// adapted bf16 value of each of the lane's columns on its own, so both tiles of a unit take the same path and the
+// last unit of an N with N % 32 == 16 (SigLIP I = 4304) simply has no b tile (b_ok false: nothing loaded or stored).
+enum { UP_NONE = 0, UP_ROPE = 1, UP_GEGLU = 2, UP_GELU = 3, UP_RESID = 4, UP_SCALE = 5 };
 struct UpEpi {
   const bf16_t* cos;
   const bf16_t* sin;
@@ -231,6 +234,9 @@ struct UpEpi {
   bf16_t* h;
   int64_t ldh;
   int rope_L, rope_D;
+  const bf16_t* res;  // RESID: added after the adapter term, row stride ldres (never aliases C)
+  int64_t ldres;
+  float post;         // SCALE
 };
 constexpr int UP_F = MAX_SEG * 2;  // k-steps of 32 a tile can need (summed: 3 segments x R / 32)
 
@@ -239,6 +245,15 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
                                                       const bf16_t* __restrict__ T, int64_t ldt, Segs S, float alpha,
                                                       UpEpi E, int64_t nunits) {
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, mi = l & 15, g = l >> 4;
+  // GELU: the bf16 gelu table in LDS, copied once per workgroup before any wave leaves (svla_gelu_rows does the same:
+  // from global memory every lookup is a scattered 2-B load)
+  __shared__ __attribute__((aligned(16))) unsigned short ltab[EPI == UP_GELU ? 2 * SVLA_GELU_TAB_N : 8];
+  if constexpr (EPI == UP_GELU) {
+    constexpr int NCH = (int)(sizeof(svla_gelu_bf16_tab) / 16);
+    for (int i = threadIdx.x; i < NCH; i += 256)
+      reinterpret_cast<u32x4*>(ltab)[i] = reinterpret_cast<const u32x4*>(svla_gelu_bf16_tab)[i];
+    __syncthreads();
+  }
   const int64_t u = (int64_t)blockIdx.x * 4 + w;
   if (u >= nunits) return;
   int64_t na, nb, lim_a = N;
@@ -296,7 +311,8 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
   const int64_t nrb = (M + 15) / 16;
   bf16x8 ta[UP_F], tb[2], ta_n[UP_F], tb_n[2];
   u32x2 ca = {0u, 0u}, cb = {0u, 0u}, ca_n = {0u, 0u}, cb_n = {0u, 0u};
-  auto load_rows = [&](int64_t rb, bf16x8(&xa)[UP_F], bf16x8(&xb)[2], u32x2& ya, u32x2& yb) {
+  u32x2 ea = {0u, 0u}, eb = {0u, 0u}, ea_n = {0u, 0u}, eb_n = {0u, 0u};  // RESID: the lane's columns of res
+  auto load_rows = [&](int64_t rb, bf16x8(&xa)[UP_F], bf16x8(&xb)[2], u32x2& ya, u32x2& yb, u32x2& za, u32x2& zb) {
     const int64_t m = rb * 16 + mi;
     const bool mok = m < M;
     const bf16_t* tr = T + (mok ? m : 0) * ldt;
@@ -321,10 +337,17 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
     yb = u32x2{0u, 0u};
     if (mok && a_ok) ya = *reinterpret_cast<const u32x2*>(cr + na + 4 * g);
     if (mok && b_ok) yb = *reinterpret_cast<const u32x2*>(cr + nb + 4 * g);
+    if constexpr (EPI == UP_RESID) {
+      const bf16_t* rr = E.res + (mok ? m : 0) * E.ldres;
+      za = u32x2{0u, 0u};
+      zb = u32x2{0u, 0u};
+      if (mok && a_ok) za = *reinterpret_cast<const u32x2*>(rr + na + 4 * g);
+      if (mok && b_ok) zb = *reinterpret_cast<const u32x2*>(rr + nb + 4 * g);
+    }
   };
 
   int64_t rb = blockIdx.y;
-  if (rb < nrb) load_rows(rb, ta_n, tb_n, ca_n, cb_n);
+  if (rb < nrb) load_rows(rb, ta_n, tb_n, ca_n, cb_n, ea_n, eb_n);
   for (; rb < nrb; rb += gridDim.y) {
 #pragma unroll
     for (int i = 0; i < UP_F; ++i) ta[i] = ta_n[i];
@@ -332,7 +355,9 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
     tb[1] = tb_n[1];
     ca = ca_n;
     cb = cb_n;
-    if (rb + gridDim.y < nrb) load_rows(rb + gridDim.y, ta_n, tb_n, ca_n, cb_n);
+    ea = ea_n;
+    eb = eb_n;
+    if (rb + gridDim.y < nrb) load_rows(rb + gridDim.y, ta_n, tb_n, ca_n, cb_n, ea_n, eb_n);
     f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
     if constexpr (!SUMMED) {
 #pragma unroll
@@ -384,6 +409,28 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int64_t M, int64_t N, bf16
         for (int i = 0; i < 4; ++i) h[i] = gelu_bf16(a[i]) * b[i];
         *reinterpret_cast<u32x2*>(E.h + m * E.ldh + na + 4 * g) = pack4(h);
       }
+    }
+    if constexpr (EPI == UP_GELU) {  // C keeps the pre-activation; h = bf16(gelu_tanh(v)): svla_gelu_rows' element formula
+      float ha[4], hb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ha[i] = gelu_bf16_lut(__float_as_uint(a[i]) >> 16, a[i], ltab);
+        hb[i] = gelu_bf16_lut(__float_as_uint(b[i]) >> 16, b[i], ltab);
+      }
+      bf16_t* hr = E.h + m * E.ldh;
+      if (a_ok) *reinterpret_cast<u32x2*>(hr + na + 4 * g) = pack4(ha);
+      if (b_ok) *reinterpret_cast<u32x2*>(hr + nb + 4 * g) = pack4(hb);
+    }
+    if constexpr (EPI == UP_RESID) {  // bf16(v + res): SVLA_EPI_BIAS_RESID's last rounding after a plain adapter add
+      float x[4], y[4];
+      unpack4(ea, x);
+      unpack4(eb, y);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] += x[i]; b[i] += y[i]; }
+    }
+    if constexpr (EPI == UP_SCALE) {  // bf16(v post): SVLA_EPI_BIAS's alpha after its bf16(acc + bias)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] *= E.post; b[i] *= E.post; }
     }
     if (a_ok) *reinterpret_cast<u32x2*>(cr + na + 4 * g) = pack4(a);
     if (b_ok) *reinterpret_cast<u32x2*>(cr + nb + 4 * g) = pack4(b);
@@ -761,7 +808,7 @@ extern "C" int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const vo
   SVLA_CHECK_ARG(mode == SVLA_LORA_SLICED ? S.ld >= S.r : S.ld >= N, "lora_up: the small matrices' ld is below their width");
   const int kind = epi ? epi->kind : SVLA_LORA_EPI_NONE;
   SVLA_CHECK_ARG(mode == SVLA_LORA_SLICED || kind == SVLA_LORA_EPI_NONE,
-                 "lora_up: the ROPE and GEGLU epilogues belong to the sliced (forward) mode");
+                 "lora_up: the epilogues belong to the sliced (forward) mode");
   UpEpi E = {};
   int64_t nunits = (N + 31) / 32;
   if (kind == SVLA_LORA_EPI_ROPE) {
@@ -798,6 +845,23 @@ extern "C" int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const vo
                      "lora_up: mx_q / mx_scales overlap c, h or each other");
       nunits = N / 64;
     }
+  } else if (kind == SVLA_LORA_EPI_GELU) {
+    // the kernel's pointers are __restrict__ and a lane stores h beside C: h may share no byte with C
+    SVLA_CHECK_ARG(S.nseg == 1 && epi->h && aligned16(epi->h) && epi->ldh % 8 == 0 && epi->ldh >= N,
+                   "lora_up: GELU needs one segment and a 16-B aligned h output with ldh % 8 == 0, ldh >= N");
+    SVLA_CHECK_ARG(!overlaps(epi->h, ((M - 1) * epi->ldh + N) * 2, c, ((M - 1) * ldc + N) * 2),
+                   "lora_up: GELU: h overlaps c");
+    E.h = (bf16_t*)epi->h;
+    E.ldh = epi->ldh;
+  } else if (kind == SVLA_LORA_EPI_RESID) {
+    SVLA_CHECK_ARG(epi->res && aligned16(epi->res) && epi->ldres % 8 == 0 && epi->ldres >= N,
+                   "lora_up: RESID needs a 16-B aligned res with ldres % 8 == 0, ldres >= N");
+    SVLA_CHECK_ARG(!overlaps(epi->res, ((M - 1) * epi->ldres + N) * 2, c, ((M - 1) * ldc + N) * 2),
+                   "lora_up: RESID: res overlaps c");
+    E.res = (const bf16_t*)epi->res;
+    E.ldres = epi->ldres;
+  } else if (kind == SVLA_LORA_EPI_SCALE) {
+    E.post = epi->post;
   } else {
     SVLA_CHECK_ARG(kind == SVLA_LORA_EPI_NONE, "lora_up: unknown epilogue %d", kind);
   }
@@ -820,6 +884,9 @@ extern "C" int svla_lora_up(int64_t M, int64_t N, void* c, int64_t ldc, const vo
   } else {
     if (kind == SVLA_LORA_EPI_ROPE) SVLA_UP(false, UP_ROPE);
     else if (kind == SVLA_LORA_EPI_GEGLU) SVLA_UP(false, UP_GEGLU);
+    else if (kind == SVLA_LORA_EPI_GELU) SVLA_UP(false, UP_GELU);
+    else if (kind == SVLA_LORA_EPI_RESID) SVLA_UP(false, UP_RESID);
+    else if (kind == SVLA_LORA_EPI_SCALE) SVLA_UP(false, UP_SCALE);
     else SVLA_UP(false, UP_NONE);
   }
 #undef SVLA_UP

@@ -1008,8 +1008,13 @@ class _LoraKernelOps:
         return t
 
     @staticmethod
-    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None):
-        K.lora_up(c, t, Bs, r, alpha=s, rope=rope, geglu_h=geglu_h, mx_out=mx_out)
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None, gelu_out=None, resid=None, post_scale=None):
+        if gelu_out is not None and not LORA_GELU_FUSED[0]:  # plain adapter add, then the GELU as its own pass
+            K.lora_up(c, t, Bs, r, alpha=s)
+            K.gelu_rows(K.GELU_TANH, c, gelu_out)
+            return
+        K.lora_up(c, t, Bs, r, alpha=s, rope=rope, geglu_h=geglu_h, mx_out=mx_out, gelu_out=gelu_out, resid=resid,
+                  post_scale=post_scale)
 
     @staticmethod
     def down_t(dy, Bs, r, s):
@@ -1049,7 +1054,7 @@ class _LoraComposedOps:
         return t
 
     @staticmethod
-    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None):
+    def up(c, t, Bs, r, s, rope=None, geglu_h=None, mx_out=None, gelu_out=None, resid=None, post_scale=None):
         R = K.lora_R(r)
         off = 0
         for i, b in enumerate(Bs):
@@ -1064,6 +1069,12 @@ class _LoraComposedOps:
             torch.mul(torch.nn.functional.gelu(c[:, :I], approximate="tanh"), c[:, I:], out=geglu_h)
             if mx_out is not None:
                 K.quant_mx_rows(geglu_h, *mx_out)
+        if gelu_out is not None:
+            gelu_out.copy_(torch.nn.functional.gelu(c, approximate="tanh"))
+        if resid is not None:
+            c += resid
+        if post_scale is not None:
+            c *= post_scale
 
     @staticmethod
     def down_t(dy, Bs, r, s):
@@ -1459,6 +1470,189 @@ class SiglipMLPFn(torch.autograd.Function):
             ctx.slot.put(dout)
             dres = None
         return dx, dres, ret_w1, ret_b1, ret_w2, ret_b2, None
+
+
+# ------------------------------------------------------------------------------------ vision-side blocks with LoRA adapters
+# The reference's default lora_target="linear" (train/spatialvla_finetune.py:264-270) also wraps the SigLIP q/k/v/
+# out_proj/fc1/fc2, the projector and both Ego3D linears.  Each base GEMM keeps its bias store (SVLA_EPI_BIAS), one
+# rank-r pass adds the adapter term and applies what the base epilogue would have applied after it (GELU, residual,
+# post-scale: svla_lora_up's GELU / RESID / SCALE); peft's bias="none" freezes weights and biases, so the backward
+# computes the adapter and input gradients only.  SVLA_LORA_KERNELS=0 runs the same Functions on the composition.
+# SVLA_LORA_GELU_FUSED=0: fc1's adapter add stores plainly and svla_gelu_rows makes the activation (two passes).
+LORA_GELU_FUSED = [os.environ.get("SVLA_LORA_GELU_FUSED", "1") != "0"]
+
+
+class SiglipAttentionLoRAFn(torch.autograd.Function):
+    """SiglipAttentionFn with a LoRA adapter on each of q, k, v, out_proj: q|k|v share one t (three segments of H
+    columns, plain adapter add after the bias GEMM), out_proj's rank-r pass adds the encoder residual (RESID)."""
+
+    @staticmethod
+    def forward(ctx, x, res, wq, bq, wk, bk, wv, bv, wo, bo, cfg: SiglipAttnCfg, scaling: float, r: int,
+                Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo, slot=None):
+        _frozen(ctx, tuple(range(2, 10)), "SiglipAttentionLoRAFn")
+        ctx.slot = slot
+        ops = _lora_ops()
+        x, res = _c(x), _c(res)
+        M, Hd = x.shape
+        t = ops.down(x, [Aq, Ak, Av], r)
+        qkv = _empty(M, 3 * Hd, like=x)
+        K.linear_fwd(x, [wq, wk, wv], qkv, kind=L.EPI_BIAS, bias=_cat_views([bq, bk, bv]))
+        ops.up(qkv, t, [Bq, Bk, Bv], r, scaling)
+        attn = _empty(M, Hd, like=x)
+        lse = _empty(cfg.B, cfg.H, cfg.L, dtype=F32, like=x)
+        a = K.attn_args(cfg.B, cfg.L, cfg.H, cfg.H, cfg.D, qkv[:, :Hd], qkv.stride(0), qkv[:, Hd:2 * Hd],
+                        qkv.stride(0), qkv[:, 2 * Hd:], qkv.stride(0), cfg.scale)
+        K.attn_fwd(a, attn, lse)
+        t_o = ops.down(attn, [Ao], r)
+        out = _empty(M, Hd, like=x)
+        K.linear_fwd(attn, [wo], out, kind=L.EPI_BIAS, bias=bo)
+        ops.up(out, t_o, [Bo], r, scaling, resid=res)
+        ctx.save_for_backward(x, wq, wk, wv, wo, qkv, attn, lse, t, t_o, Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo)
+        ctx.cfg, ctx.scaling, ctx.r = cfg, scaling, r
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, wq, wk, wv, wo, qkv, attn, lse, t, t_o, Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo = ctx.saved_tensors
+        cfg, s, r = ctx.cfg, ctx.scaling, ctx.r
+        ops = _lora_ops()
+        dout = _c(dout)
+        M, Hd = x.shape
+        nig = ctx.needs_input_grad
+        dt_o, g_o = _lora_grads(ops, dout, t_o, attn, r, s, [Bo], [Ao], nig[19:21])
+        dattn = torch.empty_like(attn)
+        K.linear_dgrad(dout, [wo], dattn)
+        ops.up_t(dattn, dt_o, [Ao], r)
+        dqkv = torch.empty_like(qkv)
+        a = K.attn_args(cfg.B, cfg.L, cfg.H, cfg.H, cfg.D, qkv[:, :Hd], qkv.stride(0), qkv[:, Hd:2 * Hd],
+                        qkv.stride(0), qkv[:, 2 * Hd:], qkv.stride(0), cfg.scale)
+        ld = dqkv.stride(0)
+        K.attn_bwd(a, attn, dattn, lse, dqkv[:, :Hd], ld, dqkv[:, Hd:2 * Hd], ld, dqkv[:, 2 * Hd:], ld)
+        dt, g_qkv = _lora_grads(ops, dqkv, t, x, r, s, [Bq, Bk, Bv], [Aq, Ak, Av], nig[13:19])
+        dx = None
+        if nig[0]:  # layer 0 reads the frozen patch embedding: nothing upstream to train
+            dx = torch.empty_like(x)
+            K.linear_dgrad(dqkv, [wq, wk, wv], dx)
+            ops.up_t(dx, dt, [Aq, Ak, Av], r)
+        dres = dout if nig[1] else None
+        if ctx.slot is not None and dres is not None:  # handed to layer_norm1's backward (ResidualSlot)
+            ctx.slot.put(dout)
+            dres = None
+        return (dx, dres, *([None] * 11), *g_qkv, *g_o, None)
+
+
+class SiglipMLPLoRAFn(torch.autograd.Function):
+    """SiglipMLPFn with a LoRA adapter on fc1 and fc2: fc1's rank-r pass leaves the adapted pre-activation in place and
+    writes gelu_tanh of it (GELU), fc2's adds the encoder residual (RESID)."""
+
+    @staticmethod
+    def forward(ctx, x, res, w1, b1, w2, b2, scaling: float, r: int, A1, B1, A2, B2, slot=None):
+        _frozen(ctx, (2, 3, 4, 5), "SiglipMLPLoRAFn")
+        ctx.slot = slot
+        ops = _lora_ops()
+        x, res = _c(x), _c(res)
+        M = x.shape[0]
+        I = w1.shape[0]
+        t1 = ops.down(x, [A1], r)
+        pre = _empty(M, I, like=x)
+        K.linear_fwd(x, [w1], pre, kind=L.EPI_BIAS, bias=b1)
+        act = _empty(M, I, like=x)
+        ops.up(pre, t1, [B1], r, scaling, gelu_out=act)
+        t2 = ops.down(act, [A2], r)
+        out = _empty(M, w2.shape[0], like=x)
+        K.linear_fwd(act, [w2], out, kind=L.EPI_BIAS, bias=b2)
+        ops.up(out, t2, [B2], r, scaling, resid=res)
+        ctx.save_for_backward(x, w1, w2, pre, act, t1, t2, A1, B1, A2, B2)
+        ctx.scaling, ctx.r = scaling, r
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w1, w2, pre, act, t1, t2, A1, B1, A2, B2 = ctx.saved_tensors
+        s, r = ctx.scaling, ctx.r
+        ops = _lora_ops()
+        dout = _c(dout)
+        nig = ctx.needs_input_grad
+        dt2, g2 = _lora_grads(ops, dout, t2, act, r, s, [B2], [A2], nig[10:12])
+        dpre = torch.empty_like(pre)
+        K.linear_dgrad(dout, [w2], dpre)
+        ops.up_t(dpre, dt2, [A2], r)  # the adapter's share enters dAct before the GELU derivative
+        K.gelu_rows(K.GELU_TANH_BWD, dpre, dpre, pre=pre)
+        dt1, g1 = _lora_grads(ops, dpre, t1, x, r, s, [B1], [A1], nig[8:10])
+        dx = None
+        if nig[0]:
+            dx = torch.empty_like(x)
+            K.linear_dgrad(dpre, [w1], dx)
+            ops.up_t(dx, dt1, [A1], r)
+        dres = dout if nig[1] else None
+        if ctx.slot is not None and dres is not None:  # handed to layer_norm2's backward (ResidualSlot)
+            ctx.slot.put(dout)
+            dres = None
+        return (dx, dres, None, None, None, None, None, None, *g1, *g2, None)
+
+
+class LinearLoRAFn(torch.autograd.Function):
+    """LinearFn with a LoRA adapter (the projector: post_scale through SCALE; Ego3D head.0: plain; head.3: the vision
+    features through RESID).  A reduction dim padded to a multiple of 8 (head.0: 204 -> 208 columns of x) pads the
+    base weight and A [r, 204] with zero columns per call; dA is trimmed back to the parameter's shape."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, res, post_scale, scaling: float, r: int, A, B):
+        _frozen(ctx, (1, 2), "LinearLoRAFn")
+        ops = _lora_ops()
+        x = _c(x)
+        M, Kx = x.shape
+        N, Kw = w.shape
+        wk, Ak = w, A
+        if Kx != Kw:
+            wk = torch.zeros(N, Kx, dtype=BF16, device=w.device)
+            wk[:, :Kw] = w
+            Ak = torch.zeros(r, Kx, dtype=BF16, device=w.device)
+            Ak[:, :Kw] = A.detach()
+        t = ops.down(x, [Ak], r)
+        y = _empty(M, N, like=x)
+        if b is not None:
+            K.linear_fwd(x, [wk], y, kind=L.EPI_BIAS, bias=b)
+        else:
+            K.linear_fwd(x, [wk], y)
+        if res is not None:
+            if post_scale != 1.0:
+                raise NotImplementedError("LinearLoRAFn: a residual together with a post-scale")
+            ops.up(y, t, [B], r, scaling, resid=_c(res))
+        else:
+            ops.up(y, t, [B], r, scaling, post_scale=post_scale if post_scale != 1.0 else None)
+        ctx.save_for_backward(x, w, A, B, t)
+        ctx.post_scale, ctx.scaling, ctx.r = post_scale, scaling, r
+        ctx.has_res = res is not None
+        ctx.wk, ctx.Ak = (wk, Ak) if wk is not w else (None, None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, A, B, t = ctx.saved_tensors
+        s, r = ctx.scaling, ctx.r
+        ops = _lora_ops()
+        dy = _c(dy)
+        nig = ctx.needs_input_grad
+        dres = dy if ctx.has_res and nig[3] else None
+        if ctx.post_scale != 1.0:
+            # y = bf16(z * post): dz = bf16(dy * post) (autograd of the reference's division), as LinearFn
+            dy = (dy * ctx.post_scale).to(BF16)
+        if ctx.Ak is None:
+            dt, (gA, gB) = _lora_grads(ops, dy, t, x, r, s, [B], [A], nig[7:9])
+        else:  # dA over the padded columns into a temporary, trimmed into the parameter's destination
+            dt, (tmp, gB) = _lora_grads(ops, dy, t, x, r, s, [B], [ctx.Ak], nig[7:9])
+            gA = None
+            if tmp is not None:
+                dA, acc, gA = _grad_dest(A, True)
+                src = tmp[:, :A.shape[1]]
+                dA.add_(src) if acc else dA.copy_(src)
+        dx = None
+        if nig[0]:
+            dx = torch.empty_like(x)
+            K.linear_dgrad(dy, [ctx.wk if ctx.wk is not None else w], dx)
+            ops.up_t(dx, dt, [ctx.Ak if ctx.Ak is not None else A], r)
+        return dx, None, None, dres, None, None, None, gA, gB
 
 
 class PatchEmbedFn(torch.autograd.Function):

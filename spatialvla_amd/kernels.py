@@ -1047,10 +1047,14 @@ def lora_down(x: torch.Tensor, mats: Sequence[torch.Tensor], r: int, t: torch.Te
 
 
 def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: int, summed: bool = False,
-            alpha: float = 1.0, rope=None, geglu_h: Optional[torch.Tensor] = None, mx_out=None):
+            alpha: float = 1.0, rope=None, geglu_h: Optional[torch.Tensor] = None, mx_out=None,
+            gelu_out: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+            post_scale: Optional[float] = None):
     """In place c = epi(bf16(c + bf16(alpha t S))): sliced (mats B_s [N_s, r], the forward) or summed (mats A_s
     [r, N]: the input gradient and the merge).  rope = (cos, sin, L, D, rotated columns); geglu_h: the GeGLU output;
-    mx_out = (q [M, N/2] e4m3, MXScales): with geglu_h, the same pass also writes h's MX copy (N/2 % 128 == 0)."""
+    mx_out = (q [M, N/2] e4m3, MXScales): with geglu_h, the same pass also writes h's MX copy (N/2 % 128 == 0).
+    The vision-side epilogues (one of them, sliced only): gelu_out [M, N] = gelu_tanh(c) with c kept as the
+    pre-activation; resid [M, N] (any row stride): c = bf16(c + resid); post_scale: c = bf16(c * post_scale)."""
     _chk_bf16(c, "lora_up c")
     _chk_bf16(t, "lora_up t")
     M, N = c.shape
@@ -1079,6 +1083,20 @@ def lora_up(c: torch.Tensor, t: torch.Tensor, mats: Sequence[torch.Tensor], r: i
         _req(tuple(geglu_h.shape) == (M, N // 2), "lora_up: h must be [M, N/2]")
         e.kind = L.LORA_EPI_GEGLU
         e.h, e.ldh = geglu_h.data_ptr(), _ld(geglu_h)
+    _req(sum(o is not None for o in (rope, geglu_h, gelu_out, resid, post_scale)) <= 1, "lora_up: one epilogue per call")
+    if gelu_out is not None:
+        _chk_bf16(gelu_out, "lora_up gelu_out")
+        _req(tuple(gelu_out.shape) == (M, N), "lora_up: gelu_out must be [M, N]")
+        e.kind = L.LORA_EPI_GELU
+        e.h, e.ldh = gelu_out.data_ptr(), _ld(gelu_out)
+    elif resid is not None:
+        _chk_bf16(resid, "lora_up resid")
+        _req(tuple(resid.shape) == (M, N), "lora_up: resid must be [M, N]")
+        e.kind = L.LORA_EPI_RESID
+        e.res, e.ldres = resid.data_ptr(), _ld(resid)
+    elif post_scale is not None:
+        e.kind = L.LORA_EPI_SCALE
+        e.post = float(post_scale)
     if mx_out is not None:  # the library checks the shapes (GEGLU only, N/2 % 128 == 0)
         q, sc = mx_out
         _req(q.dtype == FP8 and tuple(q.shape) == (M, N // 2) and q.stride(1) == 1 and sc.rows >= M

@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from . import functional as Fn
+from .modeling_gemma2 import _lora_of
 
 
 class SiglipVisionEmbeddings(nn.Module):
@@ -51,6 +52,13 @@ class SiglipAttention(nn.Module):
 
     def forward_residual(self, x2d, res2d, B, Lq, slot=None):
         cfg = Fn.SiglipAttnCfg(B, Lq, self.num_heads, self.head_dim, self.scale)
+        ads = _lora_of(self.q_proj, self.k_proj, self.v_proj, self.out_proj)
+        if ads:  # add_lora("spatialvla-linear"): adapters on q, k, v and out_proj
+            ab = [p for a in ads for p in (a.A, a.B)]
+            return Fn.SiglipAttentionLoRAFn.apply(x2d, res2d, self.q_proj.weight, self.q_proj.bias, self.k_proj.weight,
+                                                  self.k_proj.bias, self.v_proj.weight, self.v_proj.bias,
+                                                  self.out_proj.weight, self.out_proj.bias, cfg, ads[0].scaling,
+                                                  ads[0].r, *ab, slot)
         return Fn.SiglipAttentionFn.apply(x2d, res2d, self.q_proj.weight, self.q_proj.bias, self.k_proj.weight,
                                           self.k_proj.bias, self.v_proj.weight, self.v_proj.bias,
                                           self.out_proj.weight, self.out_proj.bias, cfg, slot)
@@ -66,6 +74,11 @@ class SiglipMLP(nn.Module):
         self.fc2 = nn.Linear(config.intermediate_size, config.hidden_size)
 
     def forward_residual(self, x2d, res2d, slot=None):
+        ads = _lora_of(self.fc1, self.fc2)
+        if ads:
+            ab = [p for a in ads for p in (a.A, a.B)]
+            return Fn.SiglipMLPLoRAFn.apply(x2d, res2d, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                                            ads[0].scaling, ads[0].r, *ab, slot)
         return Fn.SiglipMLPFn.apply(x2d, res2d, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, slot)
 
 

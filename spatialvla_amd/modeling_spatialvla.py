@@ -36,6 +36,10 @@ from .modeling_gemma2 import LORA_TARGETS, Gemma2ForCausalLM, Gemma2KVCache, KVM
 from .modeling_siglip import SiglipVisionModel
 
 SIGLIP_MEAN, SIGLIP_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+# the module-name suffixes the reference's default lora_target="linear" hands to peft (train/spatialvla_finetune.py:
+# 264-270), in its order; peft matches by suffix, so q_proj / k_proj / v_proj also catch the SigLIP attention
+LORA_TARGETS_FULL = ("q_proj", "o_proj", "k_proj", "v_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2",
+                     "out_proj", "linear", "position_embedding_head.0", "position_embedding_head.3")
 ZOE_MEAN, ZOE_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
 
 
@@ -67,10 +71,18 @@ class Ego3DPositionEmbeddingMLP(nn.Module):
     def forward_residual(self, feat_padded, residual2d):
         """feat_padded [N, round8(F)] (zero tail) -> residual + head(feat)."""
         h0, ln, _, h3 = self.position_embedding_head
-        x = Fn.LinearFn.apply(feat_padded, h0.weight, h0.bias, None, 1.0)
+        x = _linear(h0, feat_padded, None, 1.0)
         x = Fn.LayerNormFn.apply(x, ln.weight, ln.bias, ln.eps, None)
         x = Fn.ReLUFn.apply(x)
-        return Fn.LinearFn.apply(x, h3.weight, h3.bias, residual2d, 1.0)
+        return _linear(h3, x, residual2d, 1.0)
+
+
+def _linear(lin, x, res, post_scale):
+    """Fn.LinearFn on an nn.Linear, or Fn.LinearLoRAFn when add_lora("spatialvla-linear") attached an adapter to it."""
+    ad = getattr(lin, "lora", None)
+    if ad is None:
+        return Fn.LinearFn.apply(x, lin.weight, lin.bias, res, post_scale)
+    return Fn.LinearLoRAFn.apply(x, lin.weight, lin.bias, res, post_scale, ad.scaling, ad.r, ad.A, ad.B)
 
 
 _ZOE_CONSTS = {}
@@ -323,7 +335,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 enc = self.ego3d_features(intrinsic, depth, kinv)  # kinv: precomputed outside a graph capture
             sel = self.position_embedding_3d.forward_residual(enc, sel)
         lin = self.multi_modal_projector.linear
-        img = Fn.LinearFn.apply(sel, lin.weight, lin.bias, None, 1.0 / (self.config.text_config.hidden_size ** 0.5))
+        img = _linear(lin, sel, None, 1.0 / (self.config.text_config.hidden_size ** 0.5))
         return img.view(B, -1, img.shape[-1])
 
     # ------------------------------------------------------------------ forward
@@ -624,7 +636,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         built by the first forward and kept across optimizer steps, which rewrite the adapters only.  The KV-cached
         forward (predict_action, generate, also under enable_lora_decode) stays on its bf16 path.  Turned off, and the
         copies freed, by enable_fp8_lora(False), enable_fp8_projections(False) and merge_lora().  The captured decode
-        states are dropped."""
+        states are dropped.  With the "spatialvla-linear" set the vision side (SigLIP, projector, Ego3D) stays bf16."""
         if enabled and not self.has_lora:
             raise RuntimeError("enable_fp8_lora: no adapters attached (add_lora() / load_lora() first); a model "
                                "without adapters runs its projections in fp8 through enable_fp8_projections()")
@@ -642,9 +654,42 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                     out.append((f"language_model.model.layers.{i}.{sub}.{n}", getattr(getattr(layer, sub), n)))
         return out
 
+    def _lora_vision_linears(self):
+        """[(module path, nn.Linear)] of the vision-side linears of the reference's default target set, in the order
+        add_lora initialises them: per SigLIP encoder layer q, k, v, out_proj, fc1, fc2; the projector; Ego3D
+        position_embedding_head.0 and .3 (when the model has the Ego3D branch)."""
+        out = []
+        for i, layer in enumerate(self.vision_tower.vision_model.encoder.layers):
+            pre = f"vision_tower.vision_model.encoder.layers.{i}."
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                out.append((f"{pre}self_attn.{n}", getattr(layer.self_attn, n)))
+            for n in ("fc1", "fc2"):
+                out.append((f"{pre}mlp.{n}", getattr(layer.mlp, n)))
+        out.append(("multi_modal_projector.linear", self.multi_modal_projector.linear))
+        ego = getattr(self, "position_embedding_3d", None)
+        if ego is not None:
+            for n in (0, 3):
+                out.append((f"position_embedding_3d.position_embedding_head.{n}", ego.position_embedding_head[n]))
+        return out
+
+    def _lora_all_linears(self, vision: Optional[bool] = None):
+        """The Gemma2 projections, then (vision=True, or None = when the vision side carries adapters) the vision-side
+        linears: the fixed module order of initialisation, merge and the adapter files."""
+        if vision is None:
+            vision = self.lora_targets == "spatialvla-linear"
+        return self._lora_linears() + (self._lora_vision_linears() if vision else [])
+
     @property
     def has_lora(self) -> bool:
         return any(getattr(lin, "lora", None) is not None for _, lin in self._lora_linears())
+
+    @property
+    def lora_targets(self) -> Optional[str]:
+        """The attached target set: None, "gemma2-linear" or "spatialvla-linear"."""
+        if not self.has_lora:
+            return None
+        vis = getattr(self.multi_modal_projector.linear, "lora", None) is not None
+        return "spatialvla-linear" if vis else "gemma2-linear"
 
     @property
     def lora_decode(self) -> bool:
@@ -656,17 +701,23 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         on the training forward's rank-r kernels, every decode-step projection as svla_lora_gemv_down + svla_lora_gemv
         (9 launches per layer; DESIGN.md section 4 "LoRA").  Off (the default): those entry points refuse adapters and
         ask for merge_lora().  The captured graphs read A and B in place, so an optimizer step on them needs no
-        re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on."""
+        re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on.
+        With the "spatialvla-linear" set the prefill's SigLIP / Ego3D / projector run through their LoRA Functions under
+        no_grad, inside the captured prefill graph; the decode steps never touch the vision side."""
         self.language_model.enable_lora_decode(enabled)
         self.clear_decode_cache()
 
     def _adapter_key(self):
         """What the captured decode graphs bake in about the adapters: the switch, the first adapter's storage, its
-        rank and scaling (None without adapters)."""
+        rank and scaling, and the storage of the projector's adapter when the vision side carries adapters (the prefill
+        graph runs SigLIP, Ego3D and the projector with theirs; they are attached and rebound together) -- None without
+        adapters."""
         ad = getattr(self.language_model.model.layers[0].self_attn.q_proj, "lora", None)
         if ad is None:
             return None
-        return (self.lora_decode, ad.A.data_ptr(), ad.r, ad.scaling)
+        vis = getattr(self.multi_modal_projector.linear, "lora", None)
+        key = (self.lora_decode, ad.A.data_ptr(), ad.r, ad.scaling)
+        return key + (vis.A.data_ptr(),) if vis is not None else key
 
     def _require_merged(self, what: str):
         if self.has_lora and not self.lora_decode:
@@ -679,23 +730,36 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         lora_alpha, target_modules, init_lora_weights="gaussian"), dropout 0, get_peft_model): A [r, in] ~ N(0, 1/r^2)
         (peft "gaussian": std 1/r) and B [out, r] = 0 in bf16 on every targeted nn.Linear, every other parameter
         frozen.  Targets: the seven Gemma2 projections of every decoder layer ("gemma2-linear", or exactly those seven
-        names); the decoder layers then run Fn.GemmaAttentionLoRAFn / Fn.GemmaMLPLoRAFn.  Build the TrainEngine after
-        this call: its flat buffers then hold the adapters only."""
+        names); the decoder layers then run Fn.GemmaAttentionLoRAFn / Fn.GemmaMLPLoRAFn.  "spatialvla-linear" (or
+        exactly the reference's 13 names, LORA_TARGETS_FULL) is the reference's default lora_target="linear" as peft
+        resolves it by name suffix: the Gemma2 projections plus q/k/v/out_proj/fc1/fc2 of every SigLIP encoder layer,
+        multi_modal_projector.linear and both Ego3D linears (Fn.SiglipAttentionLoRAFn / SiglipMLPLoRAFn /
+        LinearLoRAFn).  One CPU generator seeded with `seed` is walked in the order of _lora_all_linears(): the Gemma2
+        projections layer by layer (q, k, v, o, gate, up, down), then per SigLIP layer q, k, v, out_proj, fc1, fc2,
+        then the projector, then Ego3D head.0 and head.3 -- the Gemma2 adapters of both target sets are the same
+        values under one seed.  Build the TrainEngine after this call: its flat buffers then hold the adapters only."""
         if not isinstance(r, int) or r % 8 != 0 or not 8 <= r <= 64:
             raise ValueError(f"add_lora: r must be a multiple of 8 in [8, 64], got {r!r}")
         if isinstance(target_modules, str):
-            if target_modules != "gemma2-linear":
-                raise NotImplementedError(f"add_lora: target_modules={target_modules!r}: only 'gemma2-linear' (q_proj, "
+            if target_modules not in ("gemma2-linear", "spatialvla-linear"):
+                raise NotImplementedError(f"add_lora: target_modules={target_modules!r}: 'gemma2-linear' (q_proj, "
                                           "k_proj, v_proj, o_proj, gate_proj, up_proj, down_proj of the Gemma2 decoder "
-                                          "layers) is built; SigLIP, projector, Ego3D, spatial_embed_tokens and "
-                                          "lm_head targets are not")
-            targets = set(LORA_TARGETS)
+                                          "layers) and 'spatialvla-linear' (those plus the SigLIP, projector and Ego3D "
+                                          "linears: the set the reference's lora_target='linear' resolves to) are "
+                                          "built; spatial_embed_tokens and lm_head targets are not")
+            targets = set(LORA_TARGETS if target_modules == "gemma2-linear" else LORA_TARGETS_FULL)
         else:
             targets = set(target_modules)
-        for t in sorted(targets - set(LORA_TARGETS)):
+        for t in sorted(targets - set(LORA_TARGETS_FULL)):
             raise NotImplementedError(f"add_lora: target module {t!r} is not built (only {', '.join(LORA_TARGETS)} of "
-                                      "the Gemma2 decoder layers)")
-        if targets != set(LORA_TARGETS):
+                                      "the Gemma2 decoder layers, or the reference's 13 'linear' names)")
+        vision = bool(targets - set(LORA_TARGETS))
+        if vision and targets != set(LORA_TARGETS_FULL):
+            raise NotImplementedError(f"add_lora: {sorted(targets - set(LORA_TARGETS))}: the vision side (SigLIP, "
+                                      "projector, Ego3D) is adapted as a whole, together with the Gemma2 projections: "
+                                      "pass 'spatialvla-linear' or exactly the reference's 13 names; missing "
+                                      f"{sorted(set(LORA_TARGETS_FULL) - targets)}")
+        if not vision and targets != set(LORA_TARGETS):
             raise NotImplementedError("add_lora: the seven Gemma2 projections are adapted together; missing "
                                       f"{sorted(set(LORA_TARGETS) - targets)}")
         if init != "gaussian":
@@ -712,7 +776,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             gen.seed()
         for p in self.parameters():
             p.requires_grad_(False)
-        for _, lin in self._lora_linears():
+        for _, lin in self._lora_all_linears(vision):
             w = lin.weight
             A = (torch.randn(r, w.shape[1], generator=gen) / r).to(torch.bfloat16).to(w.device)
             B = torch.zeros(w.shape[0], r, dtype=torch.bfloat16, device=w.device)
@@ -721,45 +785,62 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
 
     @torch.no_grad()
     def merge_lora(self):
-        """peft's merge_and_unload: W <- bf16(W + bf16(s B A)) on every adapted projection (svla_lora_up, summed mode,
-        C = W, T = B), then the adapters are removed and the decoder layers run their original Functions again.
+        """peft's merge_and_unload: W <- bf16(W + bf16(s B A)) on every adapted linear, Gemma2 and vision side
+        (svla_lora_up, summed mode, C = W, T = B), then the adapters are removed and every layer runs its original
+        Functions again.
         Irreversible."""
         if not self.has_lora:
             raise RuntimeError("merge_lora: no adapters attached")
         self.enable_fp8_lora(False)  # the e4m3 copies are of the unmerged base weights: the merge reads bf16
-        for _, lin in self._lora_linears():
+        for _, lin in self._lora_all_linears():
             ad = lin.lora
             w = lin.weight.data
             if w.dtype != torch.bfloat16 or not w.is_cuda:
                 raise RuntimeError("merge_lora runs on the GPU kernels: move the model to the GPU in bf16 first")
-            K.lora_up(w, ad.B.data, [ad.A.data], ad.r, summed=True, alpha=ad.scaling)
+            if w.shape[1] % 8 != 0:  # Ego3D head.0 (204 columns): svla_lora_up needs N % 8 == 0 -- a padded temporary
+                Kp = K.round_up(w.shape[1], 8)
+                wp = torch.zeros(w.shape[0], Kp, dtype=w.dtype, device=w.device)
+                wp[:, :w.shape[1]] = w
+                Ap = torch.zeros(ad.r, Kp, dtype=w.dtype, device=w.device)
+                Ap[:, :w.shape[1]] = ad.A.data
+                K.lora_up(wp, ad.B.data, [Ap], ad.r, summed=True, alpha=ad.scaling)
+                w.copy_(wp[:, :w.shape[1]])
+            else:
+                K.lora_up(w, ad.B.data, [ad.A.data], ad.r, summed=True, alpha=ad.scaling)
             del lin.lora
         Fn.WEIGHT_EPOCH[0] += 1
         self.clear_decode_cache()
 
     def save_lora(self, save_directory: str):
         """The adapters in peft's on-disk layout: adapter_model.safetensors with keys
-        base_model.model.<module path>.lora_A.weight / .lora_B.weight and adapter_config.json."""
+        base_model.model.<module path>.lora_A.weight / .lora_B.weight and adapter_config.json; every attached adapter,
+        module paths as in the reference's module tree (with the vision side attached, target_modules lists the
+        reference's 13 names)."""
         import json
         from safetensors.torch import save_file
         if not self.has_lora:
             raise RuntimeError("save_lora: no adapters attached")
         os.makedirs(save_directory, exist_ok=True)
         tensors, ad = {}, None
-        for path, lin in self._lora_linears():
+        full = self.lora_targets == "spatialvla-linear"
+        for path, lin in self._lora_all_linears():
             ad = lin.lora
             tensors[f"base_model.model.{path}.lora_A.weight"] = ad.A.detach().to("cpu").contiguous()
             tensors[f"base_model.model.{path}.lora_B.weight"] = ad.B.detach().to("cpu").contiguous()
         save_file(tensors, os.path.join(save_directory, "adapter_model.safetensors"), metadata={"format": "pt"})
-        cfg = {"peft_type": "LORA", "r": ad.r, "lora_alpha": ad.lora_alpha, "target_modules": list(LORA_TARGETS),
+        cfg = {"peft_type": "LORA", "r": ad.r, "lora_alpha": ad.lora_alpha,
+               "target_modules": list(LORA_TARGETS_FULL if full else LORA_TARGETS),
                "init_lora_weights": "gaussian", "lora_dropout": 0.0, "bias": "none", "fan_in_fan_out": False,
                "modules_to_save": None, "inference_mode": True, "task_type": None}
         with open(os.path.join(save_directory, "adapter_config.json"), "w") as f:
             json.dump(cfg, f, indent=2, sort_keys=True)
 
     def load_lora(self, load_directory: str):
-        """Attach the adapters of a save_lora() / peft directory.  Raises, listing the keys, if the file holds
-        adapters for modules outside the seven Gemma2 projections or ranks that differ between modules."""
+        """Attach the adapters of a save_lora() / peft directory: a file holding exactly the Gemma2 set
+        ("gemma2-linear") or exactly the full set of the reference's default recipe ("spatialvla-linear": Gemma2, SigLIP,
+        projector, Ego3D); whichever it holds is attached.  Raises, listing the keys, for adapters of other modules
+        (lm_head, spatial_embed_tokens), any other subset, or ranks that differ between modules; the model is then
+        left as it was."""
         import json
         import re
         from safetensors.torch import load_file
@@ -772,7 +853,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         if float(cfg.get("lora_dropout") or 0.0) != 0.0:
             raise NotImplementedError("load_lora: lora_dropout != 0 is not built")
         tensors = load_file(os.path.join(load_directory, "adapter_model.safetensors"))
-        mine = dict(self._lora_linears())
+        gemma, vis = dict(self._lora_linears()), dict(self._lora_vision_linears())
+        mine = {**gemma, **vis}
         found, foreign = {}, []
         for k, v in tensors.items():
             m = re.match(r"^base_model\.model\.(.+)\.lora_([AB])(?:\.default)?\.weight$", k)
@@ -781,11 +863,18 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 continue
             found.setdefault(m.group(1), {})[m.group(2)] = v
         if foreign:
-            raise ValueError("load_lora: adapters for modules outside the Gemma2 q/k/v/o/gate/up/down projections (or "
-                             f"unknown keys) are not built: {sorted(foreign)}")
+            raise ValueError("load_lora: adapters for modules outside the Gemma2 q/k/v/o/gate/up/down projections and the "
+                             "SigLIP / projector / Ego3D linears (or unknown keys) are not built: "
+                             f"{sorted(foreign)}")
+        full = any(p in vis for p in found)
+        if not full:
+            mine = gemma
         missing = [p for p in mine if set(found.get(p, {})) != {"A", "B"}]
         if missing:
-            raise ValueError(f"load_lora: no complete adapter for {missing}")
+            have = sorted(k for k in tensors if ".lora_" in k)
+            raise ValueError("load_lora: the file must hold exactly the Gemma2 set or exactly the full set (Gemma2, "
+                             f"SigLIP, projector, Ego3D); no complete adapter for "
+                             f"{[m + '.lora_A.weight' for m in missing]}; the file holds {have}")
         ranks = {p: int(ab["A"].shape[0]) for p, ab in found.items()}
         if len(set(ranks.values())) != 1:
             raise ValueError("load_lora: ranks differ between modules: "
@@ -795,8 +884,12 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             a, b = found[p]["A"], found[p]["B"]
             if tuple(a.shape) != (r, lin.weight.shape[1]) or tuple(b.shape) != (lin.weight.shape[0], r):
                 raise ValueError(f"load_lora: {p}: shapes {tuple(a.shape)} / {tuple(b.shape)} do not fit the projection")
+        want = "spatialvla-linear" if full else "gemma2-linear"
         if not self.has_lora:
-            self.add_lora(r, cfg.get("lora_alpha", r), seed=0)
+            self.add_lora(r, cfg.get("lora_alpha", r), target_modules=want, seed=0)
+        elif self.lora_targets != want:
+            raise ValueError(f"load_lora: the file holds the {want!r} set, the attached adapters are "
+                             f"{self.lora_targets!r} (merge_lora() first, or load into a fresh model)")
         with torch.no_grad():
             for p, lin in mine.items():
                 ad = lin.lora

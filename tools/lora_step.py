@@ -2,8 +2,10 @@
 kernels of csrc/lora.hip with the adapter gradients on the main stream (SVLA_LORA_WGRAD_STREAM=0) and on the side
 stream (the default), LoRA r = 32 on the unfused composition (SVLA_LORA_KERNELS=0's path), and the side-stream LoRA
 step with the frozen base projections in fp8 (enable_fp8_lora) -- with the flat-buffer and optimizer-state bytes of
-each and, for the fp8 leg, the bytes of the e4m3 weight copies.  The model and batches are bench.py's (same random init, same
-synthetic OXE batches)."""
+each and, for the fp8 leg, the bytes of the e4m3 weight copies.  --targets picks the adapter set of the LoRA legs:
+gemma2-linear (the seven Gemma2 projections, the default) or spatialvla-linear (those plus SigLIP, projector and Ego3D:
+the reference's default recipe); both = every LoRA leg once per set in one process, alternating.  The model and
+batches are bench.py's (same random init, same synthetic OXE batches)."""
 import argparse
 import gc
 import os
@@ -19,12 +21,12 @@ from spatialvla_amd import functional as Fn, presets
 from spatialvla_amd.engine import TrainEngine
 
 
-def run(name, cfgd, args, lora, kernels, side=False, fp8=False):
+def run(name, cfgd, args, lora, kernels, side=False, fp8=False, targets="gemma2-linear"):
     dev = torch.device("cuda", 0)
     saved = (Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0])
     model = bench.build_model(cfgd, dev)
     if lora:
-        model.add_lora(args.rank, float(args.rank), seed=0)
+        model.add_lora(args.rank, float(args.rank), target_modules=targets, seed=0)
     if fp8:
         model.enable_fp8_lora()
     Fn.LORA_KERNELS[0] = kernels
@@ -51,7 +53,7 @@ def run(name, cfgd, args, lora, kernels, side=False, fp8=False):
             if isinstance(e, dict):
                 copies += sum(e[k].numel() for k in ("q", "qt") if k in e)
                 copies += sum(e[k].buf.numel() for k in ("s", "st") if k in e and hasattr(e[k], "buf"))
-    print(f"{name:24s} {ms:8.2f} ms/step  loss {float(loss):.4f}  trainable {len(eng.params)} tensors "
+    print(f"{name:42s} {ms:8.2f} ms/step  loss {float(loss):.4f}  trainable {len(eng.params)} tensors "
           f"{eng.numel / 1e6:9.2f} M elems  flat param+grad {flat / 2**20:9.1f} MiB  optimizer state "
           f"{opt / 2**20:9.1f} MiB  peak alloc {torch.cuda.max_memory_allocated() / 2**30:6.1f} GiB"
           + (f"  e4m3 weight copies {copies / 2**20:7.1f} MiB" if fp8 else ""), flush=True)
@@ -73,6 +75,8 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=1,
                     help="repeat the list of configurations this many times, alternating them; prints min / median / max")
     ap.add_argument("--only", default="", help="comma list of: full, lora, lora-sidestream, lora-composed, lora-fp8")
+    ap.add_argument("--targets", nargs="+", default=["gemma2-linear"], choices=["gemma2-linear", "spatialvla-linear"],
+                    help="adapter set(s) of the LoRA legs; two values run every LoRA leg once per set")
     a = ap.parse_args()
     import json
     cfgd = json.loads(json.dumps(getattr(presets, a.config)()))
@@ -81,12 +85,17 @@ if __name__ == "__main__":
                         ("lora-sidestream", True, True, True), ("lora-composed", True, False, False),
                         ("lora-fp8", True, True, True, True))
             if only is None or c[0] in only]
-    times = {c[0]: [] for c in cfgs}
+    # one leg per adapter set for the LoRA configurations (the name carries the set when there are two)
+    legs = []
+    for name, lora, kern, side, *fp8 in cfgs:
+        for tg in (a.targets if lora else a.targets[:1]):
+            legs.append((f"{name}/{tg}" if lora and len(a.targets) > 1 else name, lora, kern, side, bool(fp8), tg))
+    times = {c[0]: [] for c in legs}
     for rnd in range(a.rounds):
-        for name, lora, kern, side, *fp8 in cfgs:
-            times[name].append(run(f"{name} (r={a.rank})" if lora else name, cfgd, a, lora, kern, side, bool(fp8)))
+        for name, lora, kern, side, fp8, tg in legs:
+            times[name].append(run(f"{name} (r={a.rank})" if lora else name, cfgd, a, lora, kern, side, fp8, tg))
     if a.rounds > 1:
         for name, v in times.items():
             v = sorted(v)
-            print(f"{name:24s} over {len(v)} alternating rounds: min {v[0]:.2f}  median {v[len(v) // 2]:.2f}  "
+            print(f"{name:42s} over {len(v)} alternating rounds: min {v[0]:.2f}  median {v[len(v) // 2]:.2f}  "
                   f"max {v[-1]:.2f} ms/step", flush=True)
