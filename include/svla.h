@@ -300,6 +300,37 @@ int svla_lora_gemv_down(int64_t M, int64_t K, void* x, int64_t ldx, const svla_l
 int svla_lora_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_operand* W, const void* t,
                    int64_t ldt, const svla_lora_segs* bsegs, float scaling, void* c, int64_t ldc,
                    const svla_epilogue* epi, void* stream);
+/* Adapters on both ends of the action-token path (csrc/lora_embed_head.hip): the reference's lora_target =
+ * "linear+emb" / "linear+emb+h" (train/spatialvla_finetune.py:272-286) put a peft Embedding adapter on
+ * spatial_embed_tokens (lora_embedding_A [r][na], lora_embedding_B [H][r]: the looked-up row gains
+ * s (B A)^T[id, :]) and a peft Linear adapter on lm_head.  The house rules of the kernels above hold: fp32
+ * accumulation in a fixed order, no float atomics, no block waits on another, no allocation or host sync
+ * (graph-capturable), bitwise stable run to run.  r a multiple of 8 in 8..64, any na.
+ *
+ * svla_lora_embed_fwd: after svla_embed_merge wrote out [rows][H], rewrite the rows whose id lies in [a0, a0 + na)
+ * (and that are no image slot, img_index < 0):
+ *   out[row] = bf16( bf16( bf16(bf16(embed[id] * 0) + spatial[id-a0]) + bf16(s sum_j A[j, id-a0] B[:, j]) ) * normalizer )
+ * -- svla_embed_merge's own value of the row with the adapter term added before the normalizer.  Other rows are not
+ * touched.  H % 8 == 0. */
+int svla_lora_embed_fwd(int64_t rows, int64_t H, const int64_t* ids, const int32_t* img_index, const void* embed,
+                        const void* spatial, int64_t a0, int64_t na, const void* A, const void* B, int32_t r,
+                        float scaling, float normalizer, void* out, void* stream);
+/* Its adapter gradients, g[row] = bf16(normalizer dout[row]) over the spatial rows (the CSR of svla_embed_merge_bwd:
+ * spatial_offsets[na + 1] into spatial_sorted_rows, the rows of each id in ascending order):
+ *   dA[j, id] = bf16(s sum_h (sum_{rows with that id} g[row, h]) B[h, j])   (ids that do not occur: exact zero)
+ *   dB[h, j]  = bf16(s sum_{spatial rows, in CSR order} g[row, h] A[j, id(row)])   (no spatial row: exact zeros)
+ * written, or added to the bf16 destination when `accumulate`.  Either output may be NULL. */
+int svla_lora_embed_bwd(int64_t rows, int64_t H, const int64_t* ids, const int32_t* spatial_sorted_rows,
+                        const int32_t* spatial_offsets, int64_t a0, int64_t na, const void* dout, float normalizer,
+                        const void* A, const void* B, int32_t r, float scaling, void* dA, void* dB,
+                        int32_t accumulate, void* stream);
+/* svla_softcap_ce_rows with the lm_head adapter's term added first, one trip over the raw logits [M][ld] of the
+ * plain-store GEMM: y = bf16(logits[m][n] + bf16(s sum_j T[m, j] B[n, j])) (svla_lora_up's rounding points; T [M][ldt]
+ * from svla_lora_down, B [N][r] read in place, any N), then the softcap and the row_stats of svla_softcap_ce_rows
+ * applied to y, bit for bit: with B = 0 the logits and the statistics are those of svla_softcap_ce_rows (a zero
+ * term leaves the raw logit's bits, the sign of a zero included).  Columns >= N are not written. */
+int svla_lora_softcap_ce_rows(int64_t M, int64_t N, void* logits, int64_t ld, const void* t, int64_t ldt, const void* B,
+                              int32_t r, float scaling, float cap, float* row_stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via

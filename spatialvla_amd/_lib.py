@@ -117,6 +117,12 @@ SIGNATURES = {
                                     c_i64, c_vp]),
     "svla_lora_gemv": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(Operand), c_vp, c_i64,
                                ctypes.POINTER(LoraSegs), c_f32, c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
+    "svla_lora_embed_fwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f32, c_f32,
+                                    c_vp, c_vp]),
+    "svla_lora_embed_bwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_i32, c_f32,
+                                    c_vp, c_vp, c_i32, c_vp]),
+    "svla_lora_softcap_ce_rows": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_f32, c_f32, c_vp,
+                                          c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

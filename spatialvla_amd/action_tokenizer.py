@@ -216,6 +216,71 @@ class SpatialActionTokenizer:
     def get_bin_policy(self, gs_params=None, min_sigma=0.0):
         return bin_policy_from(self.num_bins, gs_params, min_sigma)
 
+    def get_norm_meshgrid(self, bin_policy):
+        """The bin centres of a policy as two point lists in the unit cube, (translation [(m+2)(n+2)(k+2), 3],
+        rotation likewise) (reference get_norm_meshgrid, :372-388): per axis the cell midpoints with the range's two
+        ends added as one pad cell each, normalised to [0, 1] by the range; np.meshgrid's default "xy" indexing, so
+        the list runs over (axis 1, axis 0, axis 2) while its columns stay (axis 0, axis 1, axis 2)."""
+        out = []
+        for kind, axes in self.range_bins.items():
+            centres = []
+            for axis, (lo, hi) in axes.items():
+                e = np.array(bin_policy[kind][axis])
+                c = np.concatenate([[lo], 0.5 * (e[:-1] + e[1:]), [hi]])
+                centres.append((c - lo) / (hi - lo))
+            out.append(np.stack(np.meshgrid(*centres), -1).reshape(-1, 3))
+        return out[0], out[1]
+
+    def spatial_embedding_adaption(self, gs_params, embeddings, min_sigma=0.0, adpt_feature=False):
+        """Re-bin the action grid for a new robot's Gaussian action statistics (reference
+        spatial_embedding_adaption, :390-431; the --adapt_emb option of train/spatialvla_finetune.py:229-260):
+        bin_policy / min_sigma are overwritten with the policy of `gs_params` and the translation and rotation
+        tokenizers take its edges.  With adpt_feature the grid rows of `embeddings` (the model's spatial_embed_tokens,
+        an nn.Embedding) are resampled onto the new grid in place: rows [0, N) (translation) and [N, N + M) (rotation)
+        are taken as a (m, n, k, E) volume, padded by one replicated cell per side, laid on the old policy's
+        normalised bin centres (get_norm_meshgrid; its "xy" point order is paired with the volume's (m, n, k) row
+        order exactly as the reference pairs them) and interpolated at the new policy's centres with
+        scipy.interpolate.griddata(method="linear") on the float32 rows (float64 inside scipy); the pad cells are cropped
+        and the result cast float64 -> float32 -> the table's dtype.  The gripper rows stay untouched.  The device
+        table is updated with one host -> device copy.
+
+        Run it before a TrainEngine is built: the engine takes its fp32 master copy of the table at construction, so
+        a later adaption would be undone by the first optimizer step.  A weight that already is a view of an engine's
+        flat buffer (Fn.register_flat_param has seen it) raises RuntimeError."""
+        from scipy.interpolate import griddata
+        import torch
+        new_policy = self.get_bin_policy(gs_params, min_sigma=min_sigma)
+        old_grids = self.get_norm_meshgrid(self.bin_policy)
+        new_grids = self.get_norm_meshgrid(new_policy)
+        w = None
+        if adpt_feature:
+            from . import functional as Fn
+            w = embeddings.weight
+            if hasattr(w, "_svla_grad") or (w.data_ptr(), tuple(w.shape)) in Fn._FLAT_PARAMS:
+                raise RuntimeError("spatial_embedding_adaption: the table is already a view of a TrainEngine's flat "
+                                   "buffer (its fp32 master copy was taken at construction); adapt the embeddings "
+                                   "before building the engine")
+        self.bin_policy = new_policy
+        self.min_sigma = min_sigma
+        self.translation_tokenizer.set_bins(new_policy["translation"])
+        self.rotation_tokenizer.set_bins(new_policy["rotation"])
+        if not adpt_feature:
+            return
+        data = w.data
+        host = data.detach().to("cpu")
+        E = host.shape[1]
+        start = 0
+        for tok, g0, g1 in zip((self.translation_tokenizer, self.rotation_tokenizer), old_grids, new_grids):
+            m, n, k = tok.n
+            cnt = m * n * k
+            vol = host[start:start + cnt].reshape(m, n, k, E).permute(3, 0, 1, 2)
+            pad = torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1), "replicate").permute(1, 2, 3, 0).reshape(-1, E)
+            new = griddata(g0, pad.float().numpy(), g1, method="linear")
+            new = new.reshape(m + 2, n + 2, k + 2, E)[1:-1, 1:-1, 1:-1].reshape(-1, E)
+            host[start:start + cnt] = torch.from_numpy(np.ascontiguousarray(new)).to(torch.float32).to(host.dtype)
+            start += cnt
+        data.copy_(host)
+
     def __call__(self, action: np.ndarray) -> np.ndarray:
         """action (n, 7) or (7,) in [-1, 1] -> token strings (n, 3)."""
         a = np.asarray(action)

@@ -1732,6 +1732,67 @@ class EmbedMergeFn(torch.autograd.Function):
         return None, None, dimg, rsp, None, None, None, None, None
 
 
+class EmbedMergeLoRAFn(torch.autograd.Function):
+    """EmbedMergeFn with a peft Embedding adapter on the spatial table (add_lora("spatialvla-linear+emb"), reference
+    train/spatialvla_finetune.py:272-278): the row of action token id is bf16(W[id] + bf16(s sum_j A[j, id] B[:, j]))
+    before the normalizer, A [r, na] (lora_embedding_A), B [H, r] (lora_embedding_B).  The merge kernel runs as it
+    does without an adapter and svla_lora_embed_fwd rewrites the action-token rows; the backward adds dA / dB
+    (svla_lora_embed_bwd, over the CSR _merge_inputs builds) to the image-feature gradient.  The table is frozen.
+    LORA_KERNELS[0] = False: the effective table W + bf16(s (B A)^T) and its gradient's two products as torch ops
+    around the plain merge kernels."""
+
+    @staticmethod
+    def forward(ctx, ids, img_index, img_feats, spatial_w, embed_w, a0, normalizer, sort_rows, offsets, scaling, r,
+                A, B):
+        _frozen(ctx, (3, 4), "EmbedMergeLoRAFn")
+        ids = _c(ids).view(-1)
+        H = embed_w.shape[1]
+        na = spatial_w.shape[0]
+        out = _empty(ids.numel(), H, like=embed_w)
+        ctx.kernels = LORA_KERNELS[0]
+        if ctx.kernels:
+            K.embed_merge(ids, img_index, embed_w, spatial_w, a0, na, img_feats, normalizer, out)
+            K.lora_embed_fwd(ids, img_index, embed_w, spatial_w, a0, A, B, r, scaling, normalizer, out)
+        else:
+            delta = ((A.detach().float().t() @ B.detach().float().t()) * scaling).to(BF16)
+            K.embed_merge(ids, img_index, embed_w, spatial_w.detach() + delta, a0, na, img_feats, normalizer, out)
+        ctx.save_for_backward(ids, img_index, sort_rows, offsets, img_feats, A, B)
+        ctx.normalizer, ctx.na, ctx.a0, ctx.scaling, ctx.r = normalizer, na, a0, scaling, r
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ids, img_index, sort_rows, offsets, img_feats, A, B = ctx.saved_tensors
+        dout = _c(dout)
+        nig = ctx.needs_input_grad
+        dimg = torch.empty_like(img_feats) if (img_feats is not None and nig[2]) else None
+        if dimg is not None:
+            K.embed_merge_bwd(ids, img_index, sort_rows, offsets, ctx.na, dout, ctx.normalizer, None, dimg)
+        gA, accA, rA = _grad_dest(A, nig[11])
+        gB, accB, rB = _grad_dest(B, nig[12])
+        if gA is None and gB is None:
+            return (None, None, dimg) + (None,) * 10
+        if ctx.kernels:
+            if accA == accB or gA is None or gB is None:
+                K.lora_embed_bwd(ids, sort_rows, offsets, ctx.a0, ctx.na, dout, ctx.normalizer, A, B, ctx.r,
+                                 ctx.scaling, gA, gB, accumulate=accA if gA is not None else accB)
+            else:
+                K.lora_embed_bwd(ids, sort_rows, offsets, ctx.a0, ctx.na, dout, ctx.normalizer, A, B, ctx.r,
+                                 ctx.scaling, gA, None, accumulate=accA)
+                K.lora_embed_bwd(ids, sort_rows, offsets, ctx.a0, ctx.na, dout, ctx.normalizer, A, B, ctx.r,
+                                 ctx.scaling, None, gB, accumulate=accB)
+        else:
+            dsp = _empty(ctx.na, dout.shape[1], like=dout)
+            K.embed_merge_bwd(ids, img_index, sort_rows, offsets, ctx.na, dout, ctx.normalizer, dsp, None)
+            dsp = dsp.float()
+            for g, acc, val in ((gA, accA, lambda: (dsp @ B.float()).t() * ctx.scaling),
+                                (gB, accB, lambda: (dsp.t() @ A.float().t()) * ctx.scaling)):
+                if g is not None:
+                    v = val().to(BF16)
+                    g.add_(v) if acc else g.copy_(v)
+        return (None, None, dimg) + (None,) * 8 + (rA, rB)
+
+
 class LMHeadCEFn(torch.autograd.Function):
     """lm_head + final logit softcap (modeling_gemma2.py:993-997) + the shifted, masked cross-entropy of
     SpatialVLAForConditionalGeneration.forward (modeling_spatialvla.py:415-430).  Logits are written once
@@ -1740,14 +1801,70 @@ class LMHeadCEFn(torch.autograd.Function):
     Returns (logits [M, V] view, loss scalar fp32); argmax / lse are stashed on ctx-owned tensors."""
 
     @staticmethod
-    def forward(ctx, h, w, target, cap, stash):
+    def _lora_setup(ctx, n_in, scaling, r, A, B):
+        """The optional lm_head adapter (add_lora("spatialvla-linear+emb+h")): logits = bf16(W h) + bf16(s B (A h))
+        before the softcap, svla_lora_up's rounding points.  Its term is added by the pass that softcaps the raw
+        logits (svla_lora_softcap_ce_rows: one trip over the buffer instead of two); the base weight is frozen."""
+        ctx.n_in = n_in
+        ctx.lora = None
+        if A is not None:
+            _frozen(ctx, (1,), "LMHeadCEFn")
+            ctx.lora = (float(scaling), int(r))
+
+    @staticmethod
+    def _lora_softcap(logits_buf, V, stats, cap, x, lora, A, B):
+        """t = x A^T, then the adapter term, the softcap and the statistics on the raw logits; returns t."""
+        s, r = lora
+        t = _lora_ops().down(x, [A], r)
+        if LORA_KERNELS[0]:
+            K.lora_softcap_ce_rows(logits_buf, V, t, B, r, s, stats, cap)
+        else:
+            u = _empty(x.shape[0], logits_buf.shape[1], like=x)
+            K.linear_fwd(t[:, :r], [B], u[:, :V], alpha=s)
+            logits_buf[:, :V] += u[:, :V]
+            K.softcap_ce_rows(logits_buf, V, stats, cap)
+        return t
+
+    @staticmethod
+    def _lora_backward(ctx, dlog, V, x_r, t_r, A, B, dh_r):
+        """From dlog [R, ld] (zero beyond V): dt = s dlog B (a reduction over V, on the general GEMM with N = r),
+        dB = s dlog^T t (the general GEMM with r output columns), dA = dt^T x, and dh_r += dt A (svla_lora_wgrad /
+        svla_lora_up summed mode, or their compositions).  Returns (dA, dB) for autograd."""
+        s, r = ctx.lora
+        ops = _lora_ops()
+        R, ldv = dlog.shape
+        dt = torch.zeros(R, K.lora_R(r), dtype=BF16, device=dlog.device)
+        K.gemm(R, r, ldv, K._operand([dlog], L.LAYOUT_KC, k_valid=ldv), K._operand([B], L.LAYOUT_RC, k_valid=V),
+               [dt], [0], dt.stride(0), K._epi(L.EPI_STORE, alpha=s))
+        nA, nB = ctx.needs_input_grad[7], ctx.needs_input_grad[8]
+        gB, accB, rB = _grad_dest(B, nB)
+        if gB is not None:
+            K.gemm(V, r, R, K._operand([dlog[:, :V]], L.LAYOUT_RC), K._operand([_c(t_r[:, :r])], L.LAYOUT_RC),
+                   [gB], [0], r, K._epi(L.EPI_STORE, accumulate=accB, alpha=s))
+        dA = _grad_dest(A, nA)
+        if dA[0] is not None:
+            ops.wgrad(x_r, dt, [dA], r, False, 1.0, None)
+        if dh_r is not None:
+            ops.up_t(dh_r, dt, [A], r)
+        return dA[2], rB
+
+    @staticmethod
+    def _ret(ctx, dh, rw, rA=None, rB=None):
+        out = (dh, rw, None, None, None, None, None, rA, rB)
+        return out[:ctx.n_in]
+
+    @staticmethod
+    def forward(ctx, h, w, target, cap, stash, *adapter):
+        """adapter: () or (scaling, r, A [r, H], B [V, r]) -- the lm_head LoRA adapter."""
         h = _c(h)
         M = h.shape[0]
         V = w.shape[0]
         ldv = K.round_up(V, 64)
+        scaling, r, A, B = adapter if adapter else (None, 0, None, None)
+        LMHeadCEFn._lora_setup(ctx, 5 + len(adapter), scaling, r, A, B)
         rows = stash.pop("label_rows", None) if stash is not None else None
         if rows is not None:
-            return LMHeadCEFn._forward_rows(ctx, h, w, target, cap, stash, rows)
+            return LMHeadCEFn._forward_rows(ctx, h, w, target, cap, stash, rows, A, B)
         ctx.rows_only = False
         logits_buf = _empty(M, ldv, like=h)
         ntn = K.ceil_div(V, 128)
@@ -1755,7 +1872,11 @@ class LMHeadCEFn(torch.autograd.Function):
         # plain-store GEMM (the 4-wave kernel's direct epilogue), then softcap + statistics as one HBM pass: the
         # VALU-heavy SOFTCAP_CE epilogue inside the GEMM cost 13.4-13.9 ms per step against 9.2 + ~2 ms
         K.linear_fwd(h, [w], logits_buf[:, :V])
-        K.softcap_ce_rows(logits_buf, V, stats, cap)
+        t = None
+        if ctx.lora is not None:
+            t = LMHeadCEFn._lora_softcap(logits_buf, V, stats, cap, h, ctx.lora, A, B)
+        else:
+            K.softcap_ce_rows(logits_buf, V, stats, cap)
         lse = _empty(M, dtype=F32, like=h)
         argmax = _empty(M, dtype=torch.int64, like=h)
         loss_rows = _empty(M, dtype=F32, like=h)
@@ -1764,7 +1885,7 @@ class LMHeadCEFn(torch.autograd.Function):
         stash["argmax"] = argmax
         stash["lse"] = lse
         stash["n_valid"] = loss2[1:2]
-        ctx.save_for_backward(h, w, logits_buf, lse, target, loss2)
+        ctx.save_for_backward(h, w, logits_buf, lse, target, loss2, t, A, B)
         ctx.cap, ctx.V = cap, V
         ctx.row_plan = stash.pop("row_plan", None) if stash is not None else None
         ctx.mark_non_differentiable(logits_buf)
@@ -1774,7 +1895,7 @@ class LMHeadCEFn(torch.autograd.Function):
         return logits_buf[:, :V], loss2[0]
 
     @staticmethod
-    def _forward_rows(ctx, h, w, target, cap, stash, rows):
+    def _forward_rows(ctx, h, w, target, cap, stash, rows, A=None, B=None):
         """The training step's form (stash["label_rows"]: the R > 0 rows with a label, on the device, R known on the
         host): the loss is a mean over those rows and its caller reads nothing else, so the projection, the softcap
         pass and the statistics run over them alone -- the same plain-store GEMM over the gathered rows of h (each
@@ -1788,22 +1909,26 @@ class LMHeadCEFn(torch.autograd.Function):
         ldv = K.round_up(V, 64)
         h_r = _empty(R, h.shape[1], like=h)
         K.gather_rows(rows, h, h_r)
-        t_r = target.index_select(0, rows)
+        tgt_r = target.index_select(0, rows)
         logits_r = _empty(R, ldv, like=h)
         ntn = K.ceil_div(V, 128)
         stats = _empty(R, ntn, 3, dtype=F32, like=h)
         K.linear_fwd(h_r, [w], logits_r[:, :V])
-        K.softcap_ce_rows(logits_r, V, stats, cap)
+        t_r = None
+        if ctx.lora is not None:
+            t_r = LMHeadCEFn._lora_softcap(logits_r, V, stats, cap, h_r, ctx.lora, A, B)
+        else:
+            K.softcap_ce_rows(logits_r, V, stats, cap)
         lse_r = _empty(R, dtype=F32, like=h)
         argmax_r = _empty(R, dtype=torch.int64, like=h)
         loss_rows = _empty(R, dtype=F32, like=h)
         loss2 = _empty(2, dtype=F32, like=h)
-        K.ce_finalize(V, ntn, stats, logits_r[:, :V], t_r, lse_r, argmax_r, loss_rows, loss2)
+        K.ce_finalize(V, ntn, stats, logits_r[:, :V], tgt_r, lse_r, argmax_r, loss_rows, loss2)
         stash["argmax"] = torch.full((M,), -1, dtype=torch.int64, device=h.device).index_copy_(0, rows, argmax_r)
         stash["lse"] = torch.full((M,), float("nan"), dtype=F32, device=h.device).index_copy_(0, rows, lse_r)
         stash["n_valid"] = loss2[1:2]
         stash.pop("row_plan", None)
-        ctx.save_for_backward(h_r, w, logits_r, lse_r, t_r, loss2, rows)
+        ctx.save_for_backward(h_r, w, logits_r, lse_r, tgt_r, loss2, rows, t_r, A, B)
         ctx.cap, ctx.V, ctx.M = cap, V, M
         ctx.rows_only = True
         ctx.set_materialize_grads(False)
@@ -1811,24 +1936,28 @@ class LMHeadCEFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_rows(ctx, dloss):
-        h_r, w, logits_r, lse_r, t_r, loss2, rows = ctx.saved_tensors
+        h_r, w, logits_r, lse_r, tgt_r, loss2, rows, t_r, lA, lB = ctx.saved_tensors
         R, ldv = logits_r.shape
         V = ctx.V
         gscale = (dloss.float() / torch.clamp(loss2[1], min=1.0)).reshape(1).contiguous()
         dw, acc, rw = _grad_dest(w, ctx.needs_input_grad[1])
         dlog = _empty(R, ldv, like=h_r)
-        K.ce_bwd(V, logits_r[:, :V], lse_r, t_r, ctx.cap, gscale, dlog)
-        dh = None
+        K.ce_bwd(V, logits_r[:, :V], lse_r, tgt_r, ctx.cap, gscale, dlog)
+        dh, dh_r = None, None
         if ctx.needs_input_grad[0]:
             dh_r = _empty(R, h_r.shape[1], like=h_r)
             A = K._operand([dlog], L.LAYOUT_KC, k_valid=ldv)
             Bop = K._operand([w], L.LAYOUT_RC, k_valid=V)
             K.gemm(R, w.shape[1], ldv, A, Bop, [dh_r], [0], dh_r.stride(0), K._epi(L.EPI_STORE))
+        rA = rB = None
+        if ctx.lora is not None:
+            rA, rB = LMHeadCEFn._lora_backward(ctx, dlog, V, h_r, t_r, lA, lB, dh_r)
+        if dh_r is not None:
             dh = _empty(ctx.M, h_r.shape[1], like=h_r)
             K.scatter_rows(rows, dh_r, dh)
         if dw is not None:
             K.linear_wgrad(dlog[:, :V], h_r, [dw], accumulate=acc)
-        return dh, rw, None, None, None
+        return LMHeadCEFn._ret(ctx, dh, rw, rA, rB)
 
     @staticmethod
     def backward(ctx, dlogits_unused, dloss):
@@ -1838,10 +1967,10 @@ class LMHeadCEFn(torch.autograd.Function):
         therefore run over the labelled rows only: dh is zero elsewhere and dW = sum over labelled rows, the same
         values as the dense products (whose other terms are exact zeros), at 1/24 of their cost."""
         if dloss is None:  # the loss did not reach the graph's output
-            return None, None, None, None, None
+            return LMHeadCEFn._ret(ctx, None, None)
         if ctx.rows_only:
             return LMHeadCEFn._backward_rows(ctx, dloss)
-        h, w, logits_buf, lse, target, loss2 = ctx.saved_tensors
+        h, w, logits_buf, lse, target, loss2, t, lA, lB = ctx.saved_tensors
         M, ldv = logits_buf.shape
         V = ctx.V
         gscale = (dloss.float() / torch.clamp(loss2[1], min=1.0)).reshape(1).contiguous()
@@ -1859,20 +1988,33 @@ class LMHeadCEFn(torch.autograd.Function):
         if R == 0:
             if dw is not None and not acc:
                 dw.zero_()
-            return dh, rw, None, None, None
+            rets = []
+            if ctx.lora is not None:  # no label: zero adapter gradients
+                for p, need in ((lA, ctx.needs_input_grad[7]), (lB, ctx.needs_input_grad[8])):
+                    g, gacc, ret = _grad_dest(p, need)
+                    if g is not None and not gacc:
+                        g.zero_()
+                    rets.append(ret)
+            return LMHeadCEFn._ret(ctx, dh, rw, *rets)
         dlog = _empty(R, ldv, like=h)
         K.ce_bwd(V, logits_buf.index_select(0, rows)[:, :V], lse.index_select(0, rows),
                  target.index_select(0, rows).contiguous(), ctx.cap, gscale, dlog)
+        dh_r = None
         if dh is not None:
             dh_r = _empty(R, h.shape[1], like=h)
             # reduction over the padded vocab: dlog is zero in [V, ldv); W rows beyond V read as 0 (k_valid=V)
             A = K._operand([dlog], L.LAYOUT_KC, k_valid=ldv)
             Bop = K._operand([w], L.LAYOUT_RC, k_valid=V)
             K.gemm(R, w.shape[1], ldv, A, Bop, [dh_r], [0], dh_r.stride(0), K._epi(L.EPI_STORE))
+        rA = rB = None
+        if ctx.lora is not None:
+            rA, rB = LMHeadCEFn._lora_backward(ctx, dlog, V, h.index_select(0, rows).contiguous(),
+                                               t.index_select(0, rows), lA, lB, dh_r)
+        if dh is not None:
             dh.index_copy_(0, rows, dh_r)
         if dw is not None:
             K.linear_wgrad(dlog[:, :V], h.index_select(0, rows).contiguous(), [dw], accumulate=acc)
-        return dh, rw, None, None, None
+        return LMHeadCEFn._ret(ctx, dh, rw, rA, rB)
 
 
 # ------------------------------------------------------------------------------------ attention plug-in

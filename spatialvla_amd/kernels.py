@@ -1218,6 +1218,64 @@ def lora_wgrad(y: torch.Tensor, t: torch.Tensor, outs: Sequence[torch.Tensor], r
                                     1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()), "svla_lora_wgrad")
 
 
+# ------------------------------------------------------------- LoRA on spatial_embed_tokens / lm_head
+# (csrc/lora_embed_head.hip)
+def _chk_embed_adapter(A, B, r, na, H, what):
+    _chk_bf16(A, what + " A")
+    _chk_bf16(B, what + " B")
+    _req(tuple(A.shape) == (r, na) and A.is_contiguous(), f"{what}: A must be a contiguous [{r}, {na}]")
+    _req(tuple(B.shape) == (H, r) and B.is_contiguous(), f"{what}: B must be a contiguous [{H}, {r}]")
+
+
+def lora_embed_fwd(ids, img_index, embed, spatial, a0, A, B, r, scaling, normalizer, out):
+    """After embed_merge: rewrite the rows of `out` whose id lies in [a0, a0 + na) with the embedding adapter's term
+    added to the spatial row before the normalizer (svla_lora_embed_fwd)."""
+    rows, H = out.shape
+    na = spatial.shape[0]
+    _chk_bf16(out, "lora_embed_fwd out")
+    _req(out.is_contiguous() and spatial.is_contiguous() and embed.is_contiguous() and ids.numel() == rows
+         and ids.dtype == torch.int64 and (img_index is None or img_index.numel() == rows),
+         "lora_embed_fwd: contiguous tables, one int64 id per output row")
+    _chk_embed_adapter(A, B, r, na, H, "lora_embed_fwd")
+    L.check(L.lib().svla_lora_embed_fwd(rows, H, ids.data_ptr(), _ptr(img_index), embed.data_ptr(), spatial.data_ptr(),
+                                        int(a0), na, A.data_ptr(), B.data_ptr(), int(r), float(scaling),
+                                        float(normalizer), out.data_ptr(), _stream()), "svla_lora_embed_fwd")
+
+
+def lora_embed_bwd(ids, sorted_rows, offsets, a0, na, dout, normalizer, A, B, r, scaling, dA, dB, accumulate=False):
+    """The embedding adapter's gradients from dout [rows, H] over the CSR of the spatial rows (svla_lora_embed_bwd);
+    dA [r, na] / dB [H, r] are written (added to when `accumulate`); either may be None."""
+    rows, H = dout.shape
+    _chk_bf16(dout, "lora_embed_bwd dout")
+    _req(dout.is_contiguous() and ids.numel() == rows and offsets.numel() == na + 1 and sorted_rows.numel() == rows
+         and sorted_rows.dtype == torch.int32 and offsets.dtype == torch.int32, "lora_embed_bwd: CSR of the rows")
+    _chk_embed_adapter(A, B, r, na, H, "lora_embed_bwd")
+    for g, like in ((dA, A), (dB, B)):
+        _req(g is None or (g.shape == like.shape and g.dtype == BF16 and g.is_contiguous()),
+             "lora_embed_bwd: gradients must be contiguous bf16 of the adapters' shapes")
+    L.check(L.lib().svla_lora_embed_bwd(rows, H, ids.data_ptr(), sorted_rows.data_ptr(), offsets.data_ptr(), int(a0), na,
+                                        dout.data_ptr(), float(normalizer), A.data_ptr(), B.data_ptr(), int(r),
+                                        float(scaling), _ptr(dA), _ptr(dB), 1 if accumulate else 0, _stream()),
+            "svla_lora_embed_bwd")
+
+
+def lora_softcap_ce_rows(logits: torch.Tensor, N: int, t: torch.Tensor, B: torch.Tensor, r: int, scaling: float,
+                         row_stats: torch.Tensor, cap: float):
+    """softcap_ce_rows with the lm_head adapter's term bf16(scaling t B^T) added to the raw logits first, in one pass
+    (svla_lora_softcap_ce_rows); t [M, >= r] from lora_down, B [N, r]."""
+    _chk_bf16(logits, "lora_softcap_ce_rows")
+    _chk_bf16(t, "lora_softcap_ce_rows t")
+    _chk_bf16(B, "lora_softcap_ce_rows B")
+    M, ld = logits.shape[0], _ld(logits)
+    _req(row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == M * ceil_div(N, 128) * 3,
+         "lora_softcap_ce_rows: row_stats must be a contiguous fp32 [M, ceil(N/128), 3]")
+    _req(t.shape[0] == M and t.shape[1] >= r and tuple(B.shape) == (N, r) and B.is_contiguous(),
+         f"lora_softcap_ce_rows: t [{M}, >= {r}], B a contiguous [{N}, {r}]")
+    L.check(L.lib().svla_lora_softcap_ce_rows(M, N, logits.data_ptr(), ld, t.data_ptr(), _ld(t), B.data_ptr(), int(r),
+                                              float(scaling), float(cap), row_stats.data_ptr(), _stream()),
+            "svla_lora_softcap_ce_rows")
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]
 
 

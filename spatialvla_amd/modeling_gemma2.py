@@ -587,5 +587,7 @@ class Gemma2ForCausalLM(nn.Module):
         cap = float(self.config.final_logit_softcapping or 0.0)
         if cap <= 0:
             raise ValueError("final_logit_softcapping must be set for the fused softcap/CE head")
+        ad = getattr(self.lm_head, "lora", None)  # add_lora("spatialvla-linear+emb+h"): the adapter on lm_head
+        adapter = () if ad is None else (ad.scaling, ad.r, ad.A, ad.B)
         return Fn.LMHeadCEFn.apply(hidden_states.reshape(-1, hidden_states.shape[-1]), self.lm_head.weight, target,
-                                   cap, stash)
+                                   cap, stash, *adapter)

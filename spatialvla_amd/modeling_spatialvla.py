@@ -40,7 +40,32 @@ SIGLIP_MEAN, SIGLIP_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
 # 264-270), in its order; peft matches by suffix, so q_proj / k_proj / v_proj also catch the SigLIP attention
 LORA_TARGETS_FULL = ("q_proj", "o_proj", "k_proj", "v_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2",
                      "out_proj", "linear", "position_embedding_head.0", "position_embedding_head.3")
+# ... and of its lora_target="linear+emb" / "linear+emb+h" (train/spatialvla_finetune.py:272-286): also a peft Embedding
+# adapter on spatial_embed_tokens, and a Linear adapter on lm_head
+LORA_TARGETS_EMB = LORA_TARGETS_FULL + ("spatial_embed_tokens",)
+LORA_TARGETS_EMB_H = LORA_TARGETS_FULL[:7] + ("lm_head",) + LORA_TARGETS_FULL[7:] + ("spatial_embed_tokens",)
+LORA_SETS = {"gemma2-linear": LORA_TARGETS, "spatialvla-linear": LORA_TARGETS_FULL,
+             "spatialvla-linear+emb": LORA_TARGETS_EMB, "spatialvla-linear+emb+h": LORA_TARGETS_EMB_H}
+SPATIAL_TABLE = "spatial_embed_tokens"
 ZOE_MEAN, ZOE_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+
+
+class LoRAEmbeddingAdapter(nn.Module):
+    """The LoRA pair of an nn.Embedding (peft's Embedding LoRA layer): the looked-up row of id gains
+    scaling * (B A)^T[id, :] with A = lora_embedding_A [r, num_embeddings], B = lora_embedding_B [dim, r], bf16.
+    Attached as `<embedding>.lora`, so the parameters are `<embedding>.lora.A` / `.lora.B` and the base state-dict keys
+    stay as they are."""
+
+    def __init__(self, A: torch.Tensor, B: torch.Tensor, r: int, lora_alpha: float):
+        super().__init__()
+        self.A = nn.Parameter(A)
+        self.B = nn.Parameter(B)
+        self.r = int(r)
+        self.lora_alpha = float(lora_alpha)
+        self.scaling = float(lora_alpha) / int(r)
+
+    def extra_repr(self):
+        return f"r={self.r}, lora_alpha={self.lora_alpha}"
 
 
 class Ego3DPositionEmbeddingMLP(nn.Module):
@@ -378,7 +403,12 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         hidden = cfg.text_config.hidden_size
         normalizer = float(torch.tensor(hidden ** 0.5, dtype=embed_w.dtype))
         img2d = image_features.reshape(-1, image_features.shape[-1]) if image_features is not None else None
-        out = Fn.EmbedMergeFn.apply(ids, img_index, img2d, spatial_w, embed_w, a0, normalizer, sort_rows, offsets)
+        ad = self._emb_adapter
+        if ad is None:
+            out = Fn.EmbedMergeFn.apply(ids, img_index, img2d, spatial_w, embed_w, a0, normalizer, sort_rows, offsets)
+        else:  # add_lora("spatialvla-linear+emb"): the Embedding adapter on the spatial table
+            out = Fn.EmbedMergeLoRAFn.apply(ids, img_index, img2d, spatial_w, embed_w, a0, normalizer, sort_rows,
+                                            offsets, ad.scaling, ad.r, ad.A, ad.B)
         return out.view(B, Lq, hidden)
 
     def _merge_embeds(self, input_ids, inputs_embeds, image_features):
@@ -392,7 +422,12 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         if cfg.use_spatial_token and input_ids is not None:
             a0, na = int(cfg.action_token_begin_idx), int(cfg.spatial_token_num)
             sel = (input_ids >= a0) & (input_ids < a0 + na)
-            emb[sel] = emb[sel] * 0.0 + self.spatial_embed_tokens.weight[input_ids[sel] - a0]
+            sid = input_ids[sel] - a0
+            rows = self.spatial_embed_tokens.weight[sid]
+            ad = self._emb_adapter
+            if ad is not None:  # the Embedding adapter's term, bf16(W[id] + bf16(s (B A)^T[id]))
+                rows = rows + ((ad.A[:, sid].t().float() @ ad.B.t().float()) * ad.scaling).to(rows.dtype)
+            emb[sel] = emb[sel] * 0.0 + rows
         if image_features is not None:
             m = (input_ids == cfg.image_token_index).unsqueeze(-1).expand_as(emb)
             if self.strict_checks:
@@ -676,8 +711,23 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         """The Gemma2 projections, then (vision=True, or None = when the vision side carries adapters) the vision-side
         linears: the fixed module order of initialisation, merge and the adapter files."""
         if vision is None:
-            vision = self.lora_targets == "spatialvla-linear"
+            vision = getattr(self.multi_modal_projector.linear, "lora", None) is not None
         return self._lora_linears() + (self._lora_vision_linears() if vision else [])
+
+    @property
+    def _emb_adapter(self):
+        tab = self.spatial_embed_tokens
+        return getattr(tab, "lora", None) if tab is not None else None
+
+    @property
+    def _head_adapter(self):
+        return getattr(self.language_model.lm_head, "lora", None)
+
+    @property
+    def lora_modules_to_save(self) -> List[str]:
+        """peft's modules_to_save of the attached recipe: [] or ["spatial_embed_tokens"] (the spatial table trained
+        in full beside the adapters and stored in the adapter file)."""
+        return [SPATIAL_TABLE] if self.__dict__.get("_svla_modules_to_save") else []
 
     @property
     def has_lora(self) -> bool:
@@ -685,9 +735,14 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
 
     @property
     def lora_targets(self) -> Optional[str]:
-        """The attached target set: None, "gemma2-linear" or "spatialvla-linear"."""
+        """The attached target set: None, "gemma2-linear", "spatialvla-linear", "spatialvla-linear+emb" or
+        "spatialvla-linear+emb+h"."""
         if not self.has_lora:
             return None
+        if self._head_adapter is not None:
+            return "spatialvla-linear+emb+h"
+        if self._emb_adapter is not None:
+            return "spatialvla-linear+emb"
         vis = getattr(self.multi_modal_projector.linear, "lora", None) is not None
         return "spatialvla-linear" if vis else "gemma2-linear"
 
@@ -703,7 +758,12 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         ask for merge_lora().  The captured graphs read A and B in place, so an optimizer step on them needs no
         re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on.
         With the "spatialvla-linear" set the prefill's SigLIP / Ego3D / projector run through their LoRA Functions under
-        no_grad, inside the captured prefill graph; the decode steps never touch the vision side."""
+        no_grad, inside the captured prefill graph; the decode steps never touch the vision side.  A modules_to_save
+        spatial table needs nothing special (the graphs read the table in place).  With an adapter on
+        spatial_embed_tokens or lm_head ("spatialvla-linear+emb", "+emb+h") the unmerged decode is not built: turning
+        the switch on raises NotImplementedError, before any state changes -- merge_lora() first."""
+        if enabled:
+            self._refuse_emb_head_decode("enable_lora_decode")
         self.language_model.enable_lora_decode(enabled)
         self.clear_decode_cache()
 
@@ -719,13 +779,33 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         key = (self.lora_decode, ad.A.data_ptr(), ad.r, ad.scaling)
         return key + (vis.A.data_ptr(),) if vis is not None else key
 
+    def _refuse_emb_head_decode(self, what: str):
+        if self._emb_adapter is not None or self._head_adapter is not None:
+            raise NotImplementedError(f"{what}: the KV-cached decode with an unmerged adapter on spatial_embed_tokens or "
+                                      f"lm_head (the {self.lora_targets!r} set) is not built: call merge_lora() first "
+                                      "(forward without a cache and predict_action_uncached run unmerged)")
+
     def _require_merged(self, what: str):
+        self._refuse_emb_head_decode(what)
         if self.has_lora and not self.lora_decode:
             raise RuntimeError(f"{what}: call merge_lora() first (unmerged LoRA adapters; the KV-cached decode "
                                "kernels read the base weights only)")
 
+    @staticmethod
+    def _modules_to_save_arg(modules_to_save, what: str) -> bool:
+        """None, [] or "" -> False; "spatial_embed_tokens" (string or one-element list) -> True; else refused."""
+        mts = modules_to_save
+        if isinstance(mts, str):
+            mts = [m for m in mts.split("+") if m]
+        mts = list(mts or [])
+        for m in mts:
+            if m != SPATIAL_TABLE:
+                raise NotImplementedError(f"{what}: modules_to_save={m!r} is not built (only {SPATIAL_TABLE!r}, the "
+                                          "reference's --adapt_emb --adpt_feature recipe)")
+        return bool(mts)
+
     def add_lora(self, r: int, lora_alpha: float, target_modules="gemma2-linear", init: str = "gaussian",
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, modules_to_save=None):
         """LoRA fine-tuning as the reference sets it up (train/spatialvla_finetune.py:262-302: LoraConfig(r,
         lora_alpha, target_modules, init_lora_weights="gaussian"), dropout 0, get_peft_model): A [r, in] ~ N(0, 1/r^2)
         (peft "gaussian": std 1/r) and B [out, r] = 0 in bf16 on every targeted nn.Linear, every other parameter
@@ -737,22 +817,54 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         LinearLoRAFn).  One CPU generator seeded with `seed` is walked in the order of _lora_all_linears(): the Gemma2
         projections layer by layer (q, k, v, o, gate, up, down), then per SigLIP layer q, k, v, out_proj, fc1, fc2,
         then the projector, then Ego3D head.0 and head.3 -- the Gemma2 adapters of both target sets are the same
-        values under one seed.  Build the TrainEngine after this call: its flat buffers then hold the adapters only."""
+        values under one seed.  Build the TrainEngine after this call: its flat buffers then hold the adapters only.
+
+        "spatialvla-linear+emb" / "spatialvla-linear+emb+h" (or exactly the name lists of
+        train/spatialvla_finetune.py:272-286) are the reference's lora_target="linear+emb" / "linear+emb+h": the 13
+        names plus a peft Embedding adapter on spatial_embed_tokens (LoRAEmbeddingAdapter: lora_embedding_A [r, na],
+        lora_embedding_B [H, r]; Fn.EmbedMergeLoRAFn), and with "+h" an ordinary adapter on language_model.lm_head
+        (A ~ N(0, 1/r^2), B = 0; Fn.LMHeadCEFn adds bf16(s B (A h)) to the logits before the softcap).  The Embedding
+        adapter is initialised as peft initialises embeddings whatever init_lora_weights says: A = 0, B ~ N(0, 1) --
+        stated from memory of peft's reset_lora_parameters (peft is not a dependency and was not available to check
+        against).  The generator walk continues after Ego3D: spatial_embed_tokens (B only draws), then lm_head (A only
+        draws), so the 58 adapters of "spatialvla-linear" are the same bits under one seed in all three sets.
+
+        modules_to_save: None, [] or ["spatial_embed_tokens"] (also the string): the reference's --adapt_emb
+        --adpt_feature recipe, LoRA everywhere plus the spatial table trained in full (spatial_embed_tokens.weight
+        keeps requires_grad=True; Fn.EmbedMergeFn's backward produces its gradient) and stored in the adapter file.
+        Valid with any target set that does not itself adapt spatial_embed_tokens (both together: ValueError)."""
         if not isinstance(r, int) or r % 8 != 0 or not 8 <= r <= 64:
             raise ValueError(f"add_lora: r must be a multiple of 8 in [8, 64], got {r!r}")
         if isinstance(target_modules, str):
-            if target_modules not in ("gemma2-linear", "spatialvla-linear"):
+            if target_modules not in LORA_SETS:
                 raise NotImplementedError(f"add_lora: target_modules={target_modules!r}: 'gemma2-linear' (q_proj, "
                                           "k_proj, v_proj, o_proj, gate_proj, up_proj, down_proj of the Gemma2 decoder "
-                                          "layers) and 'spatialvla-linear' (those plus the SigLIP, projector and Ego3D "
-                                          "linears: the set the reference's lora_target='linear' resolves to) are "
-                                          "built; spatial_embed_tokens and lm_head targets are not")
-            targets = set(LORA_TARGETS if target_modules == "gemma2-linear" else LORA_TARGETS_FULL)
+                                          "layers), 'spatialvla-linear' (those plus the SigLIP, projector and Ego3D "
+                                          "linears: the set the reference's lora_target='linear' resolves to), "
+                                          "'spatialvla-linear+emb' (plus spatial_embed_tokens) and "
+                                          "'spatialvla-linear+emb+h' (plus lm_head) are built")
+            targets = set(LORA_SETS[target_modules])
         else:
             targets = set(target_modules)
-        for t in sorted(targets - set(LORA_TARGETS_FULL)):
+        for t in sorted(targets - set(LORA_TARGETS_EMB_H)):
             raise NotImplementedError(f"add_lora: target module {t!r} is not built (only {', '.join(LORA_TARGETS)} of "
-                                      "the Gemma2 decoder layers, or the reference's 13 'linear' names)")
+                                      "the Gemma2 decoder layers, or the reference's 'linear', 'linear+emb' or "
+                                      "'linear+emb+h' name lists)")
+        emb, head = SPATIAL_TABLE in targets, "lm_head" in targets
+        if (emb or head) and targets not in (set(LORA_TARGETS_EMB), set(LORA_TARGETS_EMB_H)):
+            raise NotImplementedError(f"add_lora: {sorted(targets & {SPATIAL_TABLE, 'lm_head'})}: spatial_embed_tokens "
+                                      "and lm_head are adapted only as the reference's 'linear+emb' / 'linear+emb+h' "
+                                      "lists: pass 'spatialvla-linear+emb', 'spatialvla-linear+emb+h' or exactly those "
+                                      "names")
+        if emb and self.spatial_embed_tokens is None:
+            raise ValueError("add_lora: the model has no spatial_embed_tokens (config.use_spatial_token is off)")
+        save_table = self._modules_to_save_arg(modules_to_save, "add_lora")
+        if save_table and emb:
+            raise ValueError("add_lora: spatial_embed_tokens is both a LoRA target and in modules_to_save; train the "
+                             "table in full (modules_to_save) or through its adapter, not both")
+        if save_table and self.spatial_embed_tokens is None:
+            raise ValueError("add_lora: modules_to_save names spatial_embed_tokens, which the model does not have")
+        targets -= {SPATIAL_TABLE, "lm_head"}
         vision = bool(targets - set(LORA_TARGETS))
         if vision and targets != set(LORA_TARGETS_FULL):
             raise NotImplementedError(f"add_lora: {sorted(targets - set(LORA_TARGETS))}: the vision side (SigLIP, "
@@ -781,14 +893,29 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             A = (torch.randn(r, w.shape[1], generator=gen) / r).to(torch.bfloat16).to(w.device)
             B = torch.zeros(w.shape[0], r, dtype=torch.bfloat16, device=w.device)
             lin.lora = LoRAAdapter(A, B, r, lora_alpha)
+        if emb:  # peft's Embedding initialisation: A = 0, B ~ N(0, 1)
+            w = self.spatial_embed_tokens.weight
+            A = torch.zeros(r, w.shape[0], dtype=torch.bfloat16, device=w.device)
+            B = torch.randn(w.shape[1], r, generator=gen).to(torch.bfloat16).to(w.device)
+            self.spatial_embed_tokens.lora = LoRAEmbeddingAdapter(A, B, r, lora_alpha)
+        if head:
+            w = self.language_model.lm_head.weight
+            A = (torch.randn(r, w.shape[1], generator=gen) / r).to(torch.bfloat16).to(w.device)
+            B = torch.zeros(w.shape[0], r, dtype=torch.bfloat16, device=w.device)
+            self.language_model.lm_head.lora = LoRAAdapter(A, B, r, lora_alpha)
+        if save_table:
+            self.spatial_embed_tokens.weight.requires_grad_(True)
+        self.__dict__["_svla_modules_to_save"] = save_table
         self.clear_decode_cache()
 
     @torch.no_grad()
     def merge_lora(self):
         """peft's merge_and_unload: W <- bf16(W + bf16(s B A)) on every adapted linear, Gemma2 and vision side
         (svla_lora_up, summed mode, C = W, T = B), then the adapters are removed and every layer runs its original
-        Functions again.
-        Irreversible."""
+        Functions again.  The lm_head adapter folds the same way (M = V rows); the Embedding adapter folds
+        W_sp[id, :] += s (B A)^T[id, :] through small transposed temporaries (C = W_sp, T = A^T [na, r], S = B^T
+        [r, H]).  A modules_to_save table simply stays as the weight; the flag is cleared and the table frozen like the
+        rest.  Irreversible."""
         if not self.has_lora:
             raise RuntimeError("merge_lora: no adapters attached")
         self.enable_fp8_lora(False)  # the e4m3 copies are of the unmerged base weights: the merge reads bf16
@@ -808,39 +935,68 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             else:
                 K.lora_up(w, ad.B.data, [ad.A.data], ad.r, summed=True, alpha=ad.scaling)
             del lin.lora
+        ad = self._emb_adapter
+        if ad is not None:
+            w = self.spatial_embed_tokens.weight.data
+            if w.dtype != torch.bfloat16 or not w.is_cuda:
+                raise RuntimeError("merge_lora runs on the GPU kernels: move the model to the GPU in bf16 first")
+            K.lora_up(w, ad.A.data.t().contiguous(), [ad.B.data.t().contiguous()], ad.r, summed=True, alpha=ad.scaling)
+            del self.spatial_embed_tokens.lora
+        ad = self._head_adapter
+        if ad is not None:
+            K.lora_up(self.language_model.lm_head.weight.data, ad.B.data, [ad.A.data], ad.r, summed=True,
+                      alpha=ad.scaling)
+            del self.language_model.lm_head.lora
+        if self.__dict__.get("_svla_modules_to_save"):
+            self.spatial_embed_tokens.weight.requires_grad_(False)
+            self.__dict__["_svla_modules_to_save"] = False
         Fn.WEIGHT_EPOCH[0] += 1
         self.clear_decode_cache()
 
     def save_lora(self, save_directory: str):
         """The adapters in peft's on-disk layout: adapter_model.safetensors with keys
         base_model.model.<module path>.lora_A.weight / .lora_B.weight and adapter_config.json; every attached adapter,
-        module paths as in the reference's module tree (with the vision side attached, target_modules lists the
-        reference's 13 names)."""
+        module paths as in the reference's module tree (target_modules lists the reference's names for the attached
+        set).  The Embedding adapter is base_model.model.spatial_embed_tokens.lora_embedding_A / .lora_embedding_B (no
+        ".weight"), the lm_head adapter base_model.model.language_model.lm_head.lora_A.weight / .lora_B.weight, and a
+        modules_to_save table base_model.model.spatial_embed_tokens.weight (peft strips "modules_to_save." and the
+        adapter name when it saves -- stated from memory of peft, which is not a dependency; load_lora accepts the
+        unstripped spellings too)."""
         import json
         from safetensors.torch import save_file
         if not self.has_lora:
             raise RuntimeError("save_lora: no adapters attached")
         os.makedirs(save_directory, exist_ok=True)
         tensors, ad = {}, None
-        full = self.lora_targets == "spatialvla-linear"
-        for path, lin in self._lora_all_linears():
+        for path, lin in self._lora_all_linears() + ([("language_model.lm_head", self.language_model.lm_head)]
+                                                      if self._head_adapter is not None else []):
             ad = lin.lora
             tensors[f"base_model.model.{path}.lora_A.weight"] = ad.A.detach().to("cpu").contiguous()
             tensors[f"base_model.model.{path}.lora_B.weight"] = ad.B.detach().to("cpu").contiguous()
+        emb = self._emb_adapter
+        if emb is not None:
+            tensors[f"base_model.model.{SPATIAL_TABLE}.lora_embedding_A"] = emb.A.detach().to("cpu").contiguous()
+            tensors[f"base_model.model.{SPATIAL_TABLE}.lora_embedding_B"] = emb.B.detach().to("cpu").contiguous()
+        mts = self.lora_modules_to_save
+        if mts:
+            tensors[f"base_model.model.{SPATIAL_TABLE}.weight"] = \
+                self.spatial_embed_tokens.weight.detach().to("cpu").contiguous()
         save_file(tensors, os.path.join(save_directory, "adapter_model.safetensors"), metadata={"format": "pt"})
         cfg = {"peft_type": "LORA", "r": ad.r, "lora_alpha": ad.lora_alpha,
-               "target_modules": list(LORA_TARGETS_FULL if full else LORA_TARGETS),
+               "target_modules": list(LORA_SETS[self.lora_targets]),
                "init_lora_weights": "gaussian", "lora_dropout": 0.0, "bias": "none", "fan_in_fan_out": False,
-               "modules_to_save": None, "inference_mode": True, "task_type": None}
+               "modules_to_save": mts or None, "inference_mode": True, "task_type": None}
         with open(os.path.join(save_directory, "adapter_config.json"), "w") as f:
             json.dump(cfg, f, indent=2, sort_keys=True)
 
     def load_lora(self, load_directory: str):
-        """Attach the adapters of a save_lora() / peft directory: a file holding exactly the Gemma2 set
-        ("gemma2-linear") or exactly the full set of the reference's default recipe ("spatialvla-linear": Gemma2, SigLIP,
-        projector, Ego3D); whichever it holds is attached.  Raises, listing the keys, for adapters of other modules
-        (lm_head, spatial_embed_tokens), any other subset, or ranks that differ between modules; the model is then
-        left as it was."""
+        """Attach the adapters of a save_lora() / peft directory: a file holding exactly one of the four sets --
+        the Gemma2 set ("gemma2-linear"), the full set of the reference's default recipe ("spatialvla-linear": Gemma2,
+        SigLIP, projector, Ego3D), that plus the spatial_embed_tokens Embedding adapter ("spatialvla-linear+emb"), or
+        that plus the lm_head adapter ("spatialvla-linear+emb+h") -- with or without a modules_to_save spatial table
+        (base_model.model.spatial_embed_tokens.weight, or peft's unstripped .modules_to_save.weight /
+        .modules_to_save.default.weight); whichever it holds is attached.  Raises, listing the keys, for adapters of
+        other modules, any other subset, or ranks that differ between modules; the model is then left as it was."""
         import json
         import re
         from safetensors.torch import load_file
@@ -848,57 +1004,96 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             cfg = json.load(f)
         if cfg.get("peft_type", "LORA") != "LORA":
             raise NotImplementedError(f"load_lora: peft_type {cfg.get('peft_type')!r}")
-        if cfg.get("modules_to_save"):
-            raise NotImplementedError(f"load_lora: modules_to_save={cfg['modules_to_save']!r} is not built")
+        cfg_table = self._modules_to_save_arg(cfg.get("modules_to_save"), "load_lora")
         if float(cfg.get("lora_dropout") or 0.0) != 0.0:
             raise NotImplementedError("load_lora: lora_dropout != 0 is not built")
         tensors = load_file(os.path.join(load_directory, "adapter_model.safetensors"))
         gemma, vis = dict(self._lora_linears()), dict(self._lora_vision_linears())
-        mine = {**gemma, **vis}
-        found, foreign = {}, []
+        head_path = "language_model.lm_head"
+        mine = {**gemma, **vis, head_path: self.language_model.lm_head}
+        found, foreign, table = {}, [], None
         for k, v in tensors.items():
             m = re.match(r"^base_model\.model\.(.+)\.lora_([AB])(?:\.default)?\.weight$", k)
-            if m is None or m.group(1) not in mine:
-                foreign.append(k)
+            if m is not None and m.group(1) in mine:
+                found.setdefault(m.group(1), {})[m.group(2)] = v
                 continue
-            found.setdefault(m.group(1), {})[m.group(2)] = v
+            m = re.match(rf"^base_model\.model\.{SPATIAL_TABLE}\.lora_embedding_([AB])(?:\.default)?$", k)
+            if m is not None and self.spatial_embed_tokens is not None:
+                found.setdefault(SPATIAL_TABLE, {})[m.group(1)] = v
+                continue
+            if self.spatial_embed_tokens is not None and re.match(
+                    rf"^base_model\.model\.{SPATIAL_TABLE}(?:\.modules_to_save(?:\.default)?)?\.weight$", k):
+                if table is not None:
+                    foreign.append(k)  # the table twice under two spellings
+                table = v
+                continue
+            foreign.append(k)
         if foreign:
-            raise ValueError("load_lora: adapters for modules outside the Gemma2 q/k/v/o/gate/up/down projections and the "
-                             "SigLIP / projector / Ego3D linears (or unknown keys) are not built: "
-                             f"{sorted(foreign)}")
-        full = any(p in vis for p in found)
-        if not full:
-            mine = gemma
-        missing = [p for p in mine if set(found.get(p, {})) != {"A", "B"}]
+            raise ValueError("load_lora: adapters for modules outside the Gemma2 q/k/v/o/gate/up/down projections, the "
+                             "SigLIP / projector / Ego3D linears, spatial_embed_tokens (lora_embedding_A/B) and lm_head "
+                             f"(or unknown keys) are not built: {sorted(foreign)}")
+        emb, head = SPATIAL_TABLE in found, head_path in found
+        full = any(p in vis for p in found) or emb or head
+        want = ("spatialvla-linear+emb+h" if head else "spatialvla-linear+emb" if emb else
+                "spatialvla-linear" if full else "gemma2-linear")
+        lin_paths = dict(gemma)
+        if full:
+            lin_paths.update(vis)
+        if head:
+            lin_paths[head_path] = self.language_model.lm_head
+        need = list(lin_paths) + ([SPATIAL_TABLE] if emb or head else [])
+        missing = [p for p in need if set(found.get(p, {})) != {"A", "B"}]
         if missing:
             have = sorted(k for k in tensors if ".lora_" in k)
-            raise ValueError("load_lora: the file must hold exactly the Gemma2 set or exactly the full set (Gemma2, "
-                             f"SigLIP, projector, Ego3D); no complete adapter for "
-                             f"{[m + '.lora_A.weight' for m in missing]}; the file holds {have}")
+            names = [m + (".lora_embedding_A" if m == SPATIAL_TABLE else ".lora_A.weight") for m in missing]
+            raise ValueError("load_lora: the file must hold exactly the Gemma2 set, the full set (Gemma2, SigLIP, "
+                             "projector, Ego3D), the full set with spatial_embed_tokens, or that with lm_head; no "
+                             f"complete adapter for {names}; the file holds {have}")
+        if emb and (table is not None or cfg_table):
+            raise ValueError("load_lora: spatial_embed_tokens is both adapted (lora_embedding_A/B) and saved in full "
+                             f"(modules_to_save); the file holds {sorted(tensors)}")
+        if cfg_table != (table is not None):
+            raise ValueError(f"load_lora: adapter_config.json says modules_to_save={cfg.get('modules_to_save')!r} but "
+                             f"the file {'holds' if table is not None else 'does not hold'} a spatial_embed_tokens "
+                             f"table; keys: {sorted(k for k in tensors if '.lora_' not in k)}")
         ranks = {p: int(ab["A"].shape[0]) for p, ab in found.items()}
         if len(set(ranks.values())) != 1:
             raise ValueError("load_lora: ranks differ between modules: "
-                             f"{ {k + '.lora_A.weight': r for k, r in sorted(ranks.items())} }")
+                             f"{ {k + ('.lora_embedding_A' if k == SPATIAL_TABLE else '.lora_A.weight'): r for k, r in sorted(ranks.items())} }")
         r = next(iter(ranks.values()))
-        for p, lin in mine.items():
+        for p, lin in lin_paths.items():
             a, b = found[p]["A"], found[p]["B"]
             if tuple(a.shape) != (r, lin.weight.shape[1]) or tuple(b.shape) != (lin.weight.shape[0], r):
                 raise ValueError(f"load_lora: {p}: shapes {tuple(a.shape)} / {tuple(b.shape)} do not fit the projection")
-        want = "spatialvla-linear" if full else "gemma2-linear"
+        if emb:
+            w = self.spatial_embed_tokens.weight
+            a, b = found[SPATIAL_TABLE]["A"], found[SPATIAL_TABLE]["B"]
+            if tuple(a.shape) != (r, w.shape[0]) or tuple(b.shape) != (w.shape[1], r):
+                raise ValueError(f"load_lora: {SPATIAL_TABLE}: shapes {tuple(a.shape)} / {tuple(b.shape)} do not fit "
+                                 "the table")
+        if table is not None and tuple(table.shape) != tuple(self.spatial_embed_tokens.weight.shape):
+            raise ValueError(f"load_lora: {SPATIAL_TABLE}.weight: shape {tuple(table.shape)} does not fit the table")
         if not self.has_lora:
-            self.add_lora(r, cfg.get("lora_alpha", r), target_modules=want, seed=0)
-        elif self.lora_targets != want:
-            raise ValueError(f"load_lora: the file holds the {want!r} set, the attached adapters are "
-                             f"{self.lora_targets!r} (merge_lora() first, or load into a fresh model)")
+            self.add_lora(r, cfg.get("lora_alpha", r), target_modules=want, seed=0,
+                          modules_to_save=[SPATIAL_TABLE] if table is not None else None)
+        elif self.lora_targets != want or bool(self.lora_modules_to_save) != (table is not None):
+            raise ValueError(f"load_lora: the file holds the {want!r} set"
+                             f"{' with' if table is not None else ' without'} a modules_to_save table, the attached "
+                             f"adapters are {self.lora_targets!r} with modules_to_save={self.lora_modules_to_save} "
+                             "(merge_lora() first, or load into a fresh model)")
+        pairs = [(lin.lora, found[p]) for p, lin in lin_paths.items()]
+        if emb:
+            pairs.append((self.spatial_embed_tokens.lora, found[SPATIAL_TABLE]))
         with torch.no_grad():
-            for p, lin in mine.items():
-                ad = lin.lora
+            for ad, ab in pairs:
                 if ad.r != r:
                     raise ValueError(f"load_lora: attached adapters have rank {ad.r}, the file has {r}")
                 ad.lora_alpha = float(cfg.get("lora_alpha", r))
                 ad.scaling = ad.lora_alpha / r
-                ad.A.copy_(found[p]["A"].to(ad.A.dtype))
-                ad.B.copy_(found[p]["B"].to(ad.B.dtype))
+                ad.A.copy_(ab["A"].to(ad.A.dtype))
+                ad.B.copy_(ab["B"].to(ad.B.dtype))
+            if table is not None:
+                self.spatial_embed_tokens.weight.copy_(table.to(self.spatial_embed_tokens.weight.dtype))
         self.clear_decode_cache()
 
     def clear_decode_cache(self):

@@ -3,9 +3,12 @@ kernels of csrc/lora.hip with the adapter gradients on the main stream (SVLA_LOR
 stream (the default), LoRA r = 32 on the unfused composition (SVLA_LORA_KERNELS=0's path), and the side-stream LoRA
 step with the frozen base projections in fp8 (enable_fp8_lora) -- with the flat-buffer and optimizer-state bytes of
 each and, for the fp8 leg, the bytes of the e4m3 weight copies.  --targets picks the adapter set of the LoRA legs:
-gemma2-linear (the seven Gemma2 projections, the default) or spatialvla-linear (those plus SigLIP, projector and Ego3D:
-the reference's default recipe); both = every LoRA leg once per set in one process, alternating.  The model and
-batches are bench.py's (same random init, same synthetic OXE batches)."""
+gemma2-linear (the seven Gemma2 projections, the default), spatialvla-linear (those plus SigLIP, projector and Ego3D:
+the reference's default recipe), spatialvla-linear+emb (plus the Embedding adapter on spatial_embed_tokens) or
+spatialvla-linear+emb+h (plus lm_head); several = every LoRA leg once per set in one process, alternating.
+--modules-to-save spatial_embed_tokens trains the spatial table in full beside the adapters (the reference's
+--adapt_emb --adpt_feature recipe; sets without the Embedding adapter only).  The model and batches are bench.py's
+(same random init, same synthetic OXE batches)."""
 import argparse
 import gc
 import os
@@ -26,7 +29,8 @@ def run(name, cfgd, args, lora, kernels, side=False, fp8=False, targets="gemma2-
     saved = (Fn.LORA_KERNELS[0], Fn.LORA_WGRAD_STREAM[0])
     model = bench.build_model(cfgd, dev)
     if lora:
-        model.add_lora(args.rank, float(args.rank), target_modules=targets, seed=0)
+        mts = args.modules_to_save if "+emb" not in targets else None
+        model.add_lora(args.rank, float(args.rank), target_modules=targets, seed=0, modules_to_save=mts)
     if fp8:
         model.enable_fp8_lora()
     Fn.LORA_KERNELS[0] = kernels
@@ -75,8 +79,11 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=1,
                     help="repeat the list of configurations this many times, alternating them; prints min / median / max")
     ap.add_argument("--only", default="", help="comma list of: full, lora, lora-sidestream, lora-composed, lora-fp8")
-    ap.add_argument("--targets", nargs="+", default=["gemma2-linear"], choices=["gemma2-linear", "spatialvla-linear"],
-                    help="adapter set(s) of the LoRA legs; two values run every LoRA leg once per set")
+    ap.add_argument("--targets", nargs="+", default=["gemma2-linear"],
+                    choices=["gemma2-linear", "spatialvla-linear", "spatialvla-linear+emb", "spatialvla-linear+emb+h"],
+                    help="adapter set(s) of the LoRA legs; several values run every LoRA leg once per set")
+    ap.add_argument("--modules-to-save", default=None, choices=["spatial_embed_tokens"],
+                    help="train the spatial table in full beside the adapters (sets without the Embedding adapter)")
     a = ap.parse_args()
     import json
     cfgd = json.loads(json.dumps(getattr(presets, a.config)()))
