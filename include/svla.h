@@ -300,6 +300,19 @@ int svla_lora_gemv_down(int64_t M, int64_t K, void* x, int64_t ldx, const svla_l
 int svla_lora_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_operand* W, const void* t,
                    int64_t ldt, const svla_lora_segs* bsegs, float scaling, void* c, int64_t ldc,
                    const svla_epilogue* epi, void* stream);
+/* svla_lora_head_gemv: the decode step's lm_head with an unmerged adapter -- peft's base(x) + lora_B(lora_A(x)) * s on
+ * lm_head (train/spatialvla_finetune.py:279-286) and the final logit softcap (model/modeling_gemma2.py:993-997) --
+ * in one pass over W [N][K] (row stride ldw), for M <= 8 rows and any N >= 1:
+ *   y[m,n]         = bf16( bf16(sum_k x[m,k] W[n,k]) + bf16(scaling sum_j T[m,j] B[n,j]) )
+ *   logits[m][n]   = softcap(y[m,n])                 ([M][ld], ld % 8 == 0, ld >= N; columns >= N are not written)
+ *   row_stats      [M][ceil(N/128)][3] = {max, sum exp, first argmax} of every 128-column group
+ * with T [M][ldt] from svla_lora_gemv_down (one segment) and B [N][ldb].  Bit for bit svla_lora_gemv (STORE) followed
+ * by svla_softcap_ce_rows on the same inputs (the same rounding points, the same summation order for the same K, the
+ * statistics' partition and combine order), so svla_ce_finalize follows unchanged and with B = 0 the result is the
+ * base decode head's.  K % 8 == 0, K <= 4096; r a multiple of 8 in 8..64; x, W, t, B, logits 16-B aligned. */
+int svla_lora_head_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* W, int64_t ldw,
+                        const void* t, int64_t ldt, const void* B, int64_t ldb, int32_t r, float scaling, float cap,
+                        void* logits, int64_t ld, float* row_stats, void* stream);
 /* Adapters on both ends of the action-token path (csrc/lora_embed_head.hip): the reference's lora_target =
  * "linear+emb" / "linear+emb+h" (train/spatialvla_finetune.py:272-286) put a peft Embedding adapter on
  * spatial_embed_tokens (lora_embedding_A [r][na], lora_embedding_B [H][r]: the looked-up row gains
@@ -315,7 +328,13 @@ int svla_lora_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, 
 int svla_lora_embed_fwd(int64_t rows, int64_t H, const int64_t* ids, const int32_t* img_index, const void* embed,
                         const void* spatial, int64_t a0, int64_t na, const void* A, const void* B, int32_t r,
                         float scaling, float normalizer, void* out, void* stream);
-/* Its adapter gradients, g[row] = bf16(normalizer dout[row]) over the spatial rows (the CSR of svla_embed_merge_bwd:
+/* svla_lora_embed_decode: svla_embed_merge (no image slot) and svla_lora_embed_fwd in one launch for the rows <= 8
+ * tokens of a decode step: out[row] is svla_embed_merge's text row, bf16(embed[id]) * normalizer, for an id outside
+ * [a0, a0 + na) and svla_lora_embed_fwd's formula inside it -- bit for bit the two kernels in sequence. */
+int svla_lora_embed_decode(int64_t rows, int64_t H, const int64_t* ids, const void* embed, const void* spatial,
+                           int64_t a0, int64_t na, const void* A, const void* B, int32_t r, float scaling,
+                           float normalizer, void* out, void* stream);
+/* svla_lora_embed_fwd's adapter gradients, g[row] = bf16(normalizer dout[row]) over the spatial rows (the CSR of svla_embed_merge_bwd:
  * spatial_offsets[na + 1] into spatial_sorted_rows, the rows of each id in ascending order):
  *   dA[j, id] = bf16(s sum_h (sum_{rows with that id} g[row, h]) B[h, j])   (ids that do not occur: exact zero)
  *   dB[h, j]  = bf16(s sum_{spatial rows, in CSR order} g[row, h] A[j, id(row)])   (no spatial row: exact zeros)

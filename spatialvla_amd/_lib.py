@@ -117,6 +117,10 @@ SIGNATURES = {
                                     c_i64, c_vp]),
     "svla_lora_gemv": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(Operand), c_vp, c_i64,
                                ctypes.POINTER(LoraSegs), c_f32, c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
+    "svla_lora_head_gemv": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_f32,
+                                    c_f32, c_vp, c_i64, c_vp, c_vp]),
+    "svla_lora_embed_decode": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f32, c_f32,
+                                       c_vp, c_vp]),
     "svla_lora_embed_fwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f32, c_f32,
                                     c_vp, c_vp]),
     "svla_lora_embed_bwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_i32, c_f32,

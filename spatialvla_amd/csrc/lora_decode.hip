@@ -1,5 +1,5 @@
-// Decode-step (M <= 8 token rows) projections with unmerged LoRA adapters for gfx950 (MI355X): svla_lora_gemv_down and
-// svla_lora_gemv (include/svla.h).
+// Decode-step (M <= 8 token rows) projections with unmerged LoRA adapters for gfx950 (MI355X): svla_lora_gemv_down,
+// svla_lora_gemv and svla_lora_head_gemv (include/svla.h).
 //
 // A decode step is bound by launch latency, not bytes (a layer streams ~200 MB of base weights next to ~3 MB of
 // adapters), so the adapter arithmetic rides inside the GEMVs that stream the base weights instead of the training
@@ -9,13 +9,16 @@
 //                        in its prologue (h and x are then stored for the projection that follows);
 //   svla_lora_gemv       y = bf16(bf16(x W^T) + bf16(s T B_s^T)), one wave per output row (or gate|up row pair): the
 //                        wave's B row (<= 128 B) and the M r values of T are loaded with its weight prefetch, the
-//                        rank-r dot product is one value per lane and a butterfly.
+//                        rank-r dot product is one value per lane and a butterfly;
+//   svla_lora_head_gemv  the lm_head form of svla_lora_gemv: a block owns 128 consecutive vocabulary rows, keeps their
+//                        raw logits in LDS and finishes them with svla_softcap_ce_rows' per-lane unit (softcap, store,
+//                        the group's max / sum exp / first argmax), so a decode step's head is T, this, finalize.
 // The base dot products keep the chunk map and summation order of gemm.hip's GEMVs (gemv_kernel / gemv_pf_kernel /
 // gemv_splitk_kernel / gemv_norm2_kernel) for the same K, so with B = 0 the outputs are those kernels' bits, and the
 // rounding points are svla_gemm_bf16 (plain store) followed by svla_lora_up (SLICED).
 // fp32 accumulation in a fixed order, 16-B non-temporal weight reads issued before the first FMA, no atomics, no
 // block waits for another block, no allocation and no host synchronisation (graph-capturable).
-#include "svla_common.h"
+#include "softcap_tab.h"
 
 namespace {
 
@@ -472,6 +475,147 @@ __global__ __launch_bounds__(256) void lg_split_kernel(int M, int64_t rows, int6
   }
 }
 
+// ------------------------------------------------------------------------------------------------ lora_head_gemv
+// A block owns LH_COLS = 128 consecutive output rows n (vocabulary entries): one statistics group of
+// svla_softcap_ce_rows.  Wave w walks rows w, w + 4, ... of the block with lg_kernel's per-row dot product (the lane's
+// chunks k = 8 lane + 512 i in order, then the wave butterfly; KCH covers K, chunks at or beyond K are skipped, so the
+// order is that of lg_kernel's KCH = 4 / 5 / loop forms for the same K), the next row's weights and B row in flight
+// while this one is summed; lane 0 leaves y = bf16(bf16(base) + bf16(s T B)) in LDS.  Then 16 lanes per token row run
+// the per-element unit of softcap.hip (8 columns per lane in scan order, the 16-lane DPP butterfly of its group
+// combine) on the block's [M][128] raw values: logits and statistics are svla_softcap_ce_rows' bits on y.
+constexpr int LH_COLS = 128;
+constexpr int LH_MAX_K = 4096;
+
+template <int CTRL>
+__device__ __forceinline__ int lh_dpp(int x) {
+  return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float lh_dppf(float x) {
+  return __int_as_float(lh_dpp<CTRL>(__float_as_int(x)));
+}
+constexpr int LH_X1 = 0xb1, LH_X2 = 0x4e, LH_HALF_MIRROR = 0x141, LH_MIRROR = 0x140;  // softcap.hip's group butterfly
+
+template <int KCH, int MR>
+__global__ __launch_bounds__(256) void lh_kernel(int M, int64_t N, int64_t K, const bf16_t* __restrict__ x, int64_t ldx,
+                                                 const bf16_t* __restrict__ W, int64_t ldw,
+                                                 const bf16_t* __restrict__ T, int64_t ldt,
+                                                 const bf16_t* __restrict__ B, int64_t ldb, int r, float sc, float cap,
+                                                 bf16_t* __restrict__ lg, int64_t ld, float* __restrict__ row_stats) {
+  __shared__ __attribute__((aligned(16))) unsigned short tab[TANH_TAB_BYTES / 2 + 8];
+  __shared__ __attribute__((aligned(16))) bf16_t ys[LG_MAXM][LH_COLS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid < TANH_TAB_BYTES / 16)
+    reinterpret_cast<u32x4*>(tab)[tid] = reinterpret_cast<const u32x4*>(svla_tanh_bf16_tab)[tid];
+  const int64_t n0 = (int64_t)blockIdx.x * LH_COLS;
+  const int nrow = (int)(N - n0 < LH_COLS ? N - n0 : LH_COLS);
+  const bool on = lane < r;
+  float tv[MR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) tv[m] = (on && m < M) ? bf2f(T[m * ldt + lane]) : 0.f;
+  auto load_row = [&](int64_t n, u32x4 (&w)[KCH], float& b) {
+    const bf16_t* wr = W + n * ldw;
+#pragma unroll
+    for (int i = 0; i < KCH; ++i) {
+      const int64_t k = (int64_t)lane * 8 + i * 512;
+      w[i] = k < K ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wr + k)) : u32x4{0, 0, 0, 0};
+    }
+    b = on ? bf2f(B[n * ldb + lane]) : 0.f;
+  };
+  u32x4 wc[KCH], wn[KCH];
+  float bc = 0.f, bn = 0.f;
+  if (wv < nrow) load_row(n0 + wv, wc, bc);
+  for (int i = wv; i < nrow; i += 4) {  // wave-uniform
+    if (i + 4 < nrow) load_row(n0 + i + 4, wn, bn);
+    float acc[MR];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) acc[m] = 0.f;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      const int64_t k = (int64_t)lane * 8 + c * 512;
+      if (k < K) {
+        float wf[8];
+        unpack8(wc[c], wf);
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+          if (m < M) {
+            float xf[8];
+            unpack8(*reinterpret_cast<const u32x4*>(x + m * ldx + k), xf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[m] = fmaf(wf[e], xf[e], acc[m]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      if (m < M) {
+        const float base = wave_sum(acc[m]);
+        const float l = wave_sum(bc * tv[m]);
+        const float y = round_bf(round_bf(base) + round_bf(sc * l));  // ad_finish
+        if (lane == 0) ys[m][i] = f2bf(y);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) wc[c] = wn[c];
+    bc = bn;
+  }
+  __syncthreads();
+  if (tid >= 16 * LG_MAXM) return;  // whole waves leave
+  // softcap + statistics: token row m = tid / 16, columns n .. n + 7 of the block's group (softcap.hip's partition)
+  const float icap = 1.0f / cap;
+  const int m = tid >> 4, l16 = tid & 15;
+  const int64_t n = n0 + 8 * l16;
+  const int64_t nv = m < M ? N - n : 0;  // >= 8 whole chunk, 1..7 ragged row end, <= 0 none
+  float mx = -INFINITY, se = 0.f;
+  int am = 0x7fffffff;
+  if (nv > 0) {
+    bf16_t* p = lg + m * ld + n;
+    float v[8];
+    if (nv >= 8) {
+      unpack8(*reinterpret_cast<const u32x4*>(&ys[m][8 * l16]), v);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = i < nv ? bf2f(ys[m][8 * l16 + i]) : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      v[i] = softcap_bf16_tab<const unsigned short*, true>(v[i], cap, icap, tab);
+      if (i < nv && v[i] > mx) { mx = v[i]; am = (int)(n + i); }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (i < nv) se += __expf(v[i] - mx);
+    if (nv >= 8) {
+      *reinterpret_cast<u32x4*>(p) = pack8(v);
+    } else {
+      for (int i = 0; i < nv; ++i) p[i] = f2bf(v[i]);
+    }
+    if (mx == -INFINITY) se = 0.f;
+  }
+  float gm = mx;
+  gm = fmaxf(gm, lh_dppf<LH_X1>(gm));
+  gm = fmaxf(gm, lh_dppf<LH_X2>(gm));
+  gm = fmaxf(gm, lh_dppf<LH_HALF_MIRROR>(gm));
+  gm = fmaxf(gm, lh_dppf<LH_MIRROR>(gm));
+  se = (mx == -INFINITY) ? 0.f : se * __expf(mx - gm);
+  am = (mx == gm) ? am : 0x7fffffff;
+  se += lh_dppf<LH_X1>(se);
+  am = min(am, lh_dpp<LH_X1>(am));
+  se += lh_dppf<LH_X2>(se);
+  am = min(am, lh_dpp<LH_X2>(am));
+  se += lh_dppf<LH_HALF_MIRROR>(se);
+  am = min(am, lh_dpp<LH_HALF_MIRROR>(am));
+  se += lh_dppf<LH_MIRROR>(se);
+  am = min(am, lh_dpp<LH_MIRROR>(am));
+  if (l16 == 0 && nv > 0) {
+    float* rs = row_stats + (m * ((N + 127) / 128) + n / 128) * 3;
+    rs[0] = gm;
+    rs[1] = se;
+    rs[2] = __int_as_float(am);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -623,4 +767,37 @@ extern "C" int svla_lora_gemv(int64_t M, int64_t N, int64_t K, const void* x, in
 #undef SVLA_LG
 #undef SVLA_LG1
   return svla::check_launch("lora_gemv");
+}
+
+extern "C" int svla_lora_head_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* W,
+                                   int64_t ldw, const void* t, int64_t ldt, const void* B, int64_t ldb, int32_t r,
+                                   float scaling, float cap, void* logits, int64_t ld, float* row_stats, void* stream) {
+  SVLA_CHECK_ARG(M >= 1 && M <= LG_MAXM && N >= 1 && N < (1ll << 31) && K >= 8 && K % 8 == 0 && K <= LH_MAX_K,
+                 "lora_head_gemv: M in [1, %d], N >= 1, K a multiple of 8 in [8, %d] (M %lld, N %lld, K %lld)", LG_MAXM,
+                 LH_MAX_K, (long long)M, (long long)N, (long long)K);
+  SVLA_CHECK_ARG(x && W && t && B && logits && row_stats, "lora_head_gemv: NULL argument");
+  SVLA_CHECK_ARG(aligned16(x) && aligned16(W) && aligned16(t) && aligned16(B) && aligned16(logits),
+                 "lora_head_gemv: x / W / t / B / logits not 16-B aligned");
+  SVLA_CHECK_ARG(r >= 8 && r <= MAX_R && r % 8 == 0, "lora_head_gemv: rank must be a multiple of 8 in [8, 64], got %d",
+                 (int)r);
+  SVLA_CHECK_ARG(ldx % 8 == 0 && ldx >= K && ldw % 8 == 0 && ldw >= K, "lora_head_gemv: ldx, ldw multiples of 8 >= K");
+  SVLA_CHECK_ARG(ldb % 8 == 0 && ldb >= r && ldt % 8 == 0 && ldt >= r, "lora_head_gemv: ldb, ldt multiples of 8 >= r");
+  SVLA_CHECK_ARG(ld % 8 == 0 && ld >= N && cap > 0.f, "lora_head_gemv: ld (multiple of 8 >= N), cap > 0");
+  const int kch = (int)((K + 511) / 512);
+  const dim3 grid((unsigned)((N + LH_COLS - 1) / LH_COLS)), block(256);
+#define SVLA_LH1(KC, MR_)                                                                                             \
+  hipLaunchKernelGGL((lh_kernel<KC, MR_>), grid, block, 0, (hipStream_t)stream, (int)M, N, K, (const bf16_t*)x, ldx,  \
+                     (const bf16_t*)W, ldw, (const bf16_t*)t, ldt, (const bf16_t*)B, ldb, (int)r, scaling, cap,       \
+                     (bf16_t*)logits, ld, row_stats)
+#define SVLA_LH(KC)                  \
+  do {                               \
+    if (M == 1) SVLA_LH1(KC, 1);     \
+    else SVLA_LH1(KC, LG_MAXM);      \
+  } while (0)
+  if (kch <= 1) SVLA_LH(1);
+  else if (kch <= 5) SVLA_LH(5);
+  else SVLA_LH(8);
+#undef SVLA_LH
+#undef SVLA_LH1
+  return svla::check_launch("lora_head_gemv");
 }

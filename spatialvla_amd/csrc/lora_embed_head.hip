@@ -1,7 +1,7 @@
 // LoRA adapters on both ends of the action-token path, gfx950 (MI355X): the peft Embedding adapter on
 // spatial_embed_tokens and the peft Linear adapter on lm_head of the reference's lora_target = "linear+emb" /
-// "linear+emb+h" (train/spatialvla_finetune.py:272-286) -- svla_lora_embed_fwd, svla_lora_embed_bwd,
-// svla_lora_softcap_ce_rows (include/svla.h).  fp32 accumulation in a fixed order, no atomics, no block waits on
+// "linear+emb+h" (train/spatialvla_finetune.py:272-286) -- svla_lora_embed_fwd, svla_lora_embed_decode,
+// svla_lora_embed_bwd, svla_lora_softcap_ce_rows (include/svla.h).  fp32 accumulation in a fixed order, no atomics, no block waits on
 // another, no allocation or host sync, bitwise stable run to run.
 //
 // The embedding kernels touch the few hundred action-token rows of a batch only (one block per row / per table id);
@@ -48,6 +48,53 @@ __global__ __launch_bounds__(256) void lora_embed_fwd_kernel(int64_t H, const in
         for (int j = 0; j < 8; ++j) acc += a[j0 + j] * b[j];
       }
       const float base = round_bf(round_bf(e[i] * 0.0f) + v[i]);  // svla_embed_merge's value of the row
+      v[i] = round_bf(base + round_bf(s * acc)) * normalizer;
+    }
+    *reinterpret_cast<u32x4*>(out + row * H + ch * 8) = pack8(v);
+  }
+}
+
+// ------------------------------------------------------------------ embedding forward, decode step
+// svla_embed_merge (no image slot) and lora_embed_fwd_kernel in one launch for the few token rows of a decode step:
+// a text id takes the merge kernel's expression, an action-token id the kernel's above, operand for operand, so the
+// row is bitwise what the two launches leave.
+__global__ __launch_bounds__(256) void lora_embed_decode_kernel(int64_t H, const int64_t* __restrict__ ids,
+                                                                const bf16_t* __restrict__ embed,
+                                                                const bf16_t* __restrict__ spatial, int64_t a0,
+                                                                int64_t na, const bf16_t* __restrict__ A,
+                                                                const bf16_t* __restrict__ B, int r, float s,
+                                                                float normalizer, bf16_t* __restrict__ out) {
+  const int64_t row = blockIdx.x;
+  const int64_t id = ids[row];
+  if (id < a0 || id >= a0 + na) {  // block-uniform: embed_merge_kernel's text row
+    for (int64_t ch = threadIdx.x; ch < (H >> 3); ch += blockDim.x) {
+      float v[8];
+      unpack8(*reinterpret_cast<const u32x4*>(embed + id * H + ch * 8), v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = round_bf(v[j]) * normalizer;
+      *reinterpret_cast<u32x4*>(out + row * H + ch * 8) = pack8(v);
+    }
+    return;
+  }
+  const int64_t sid = id - a0;
+  __shared__ float a[EH_MAXR];
+  if ((int)threadIdx.x < r) a[threadIdx.x] = bf2f(A[(int64_t)threadIdx.x * na + sid]);
+  __syncthreads();
+  for (int64_t ch = threadIdx.x; ch < (H >> 3); ch += blockDim.x) {
+    float e[8], v[8];
+    unpack8(*reinterpret_cast<const u32x4*>(embed + id * H + ch * 8), e);
+    unpack8(*reinterpret_cast<const u32x4*>(spatial + sid * H + ch * 8), v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const bf16_t* brow = B + (ch * 8 + i) * r;
+      float acc = 0.f;
+      for (int j0 = 0; j0 < r; j0 += 8) {
+        float b[8];
+        unpack8(*reinterpret_cast<const u32x4*>(brow + j0), b);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += a[j0 + j] * b[j];
+      }
+      const float base = round_bf(round_bf(e[i] * 0.0f) + v[i]);
       v[i] = round_bf(base + round_bf(s * acc)) * normalizer;
     }
     *reinterpret_cast<u32x4*>(out + row * H + ch * 8) = pack8(v);
@@ -295,6 +342,19 @@ extern "C" int svla_lora_embed_fwd(int64_t rows, int64_t H, const int64_t* ids, 
                      (const bf16_t*)embed, (const bf16_t*)spatial, a0, na, (const bf16_t*)A, (const bf16_t*)B, (int)r,
                      scaling, normalizer, (bf16_t*)out);
   return svla::check_launch("lora_embed_fwd");
+}
+
+extern "C" int svla_lora_embed_decode(int64_t rows, int64_t H, const int64_t* ids, const void* embed, const void* spatial,
+                                      int64_t a0, int64_t na, const void* A, const void* B, int32_t r, float scaling,
+                                      float normalizer, void* out, void* stream) {
+  SVLA_CHECK_ARG(rows >= 1 && rows <= 8 && H > 0 && H % 8 == 0 && na > 0, "lora_embed_decode: rows in [1, 8], H %% 8, na");
+  SVLA_CHECK_ARG(rank_ok(r), "lora_embed_decode: r must be a multiple of 8 in [8, 64], got %d", (int)r);
+  SVLA_CHECK_ARG(ids && embed && spatial && A && B && out, "lora_embed_decode: null pointer");
+  SVLA_CHECK_ARG(al16(embed) && al16(spatial) && al16(B) && al16(out), "lora_embed_decode: 16-B aligned tables");
+  hipLaunchKernelGGL(lora_embed_decode_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, H, ids,
+                     (const bf16_t*)embed, (const bf16_t*)spatial, a0, na, (const bf16_t*)A, (const bf16_t*)B, (int)r,
+                     scaling, normalizer, (bf16_t*)out);
+  return svla::check_launch("lora_embed_decode");
 }
 
 extern "C" int svla_lora_embed_bwd(int64_t rows, int64_t H, const int64_t* ids, const int32_t* spatial_sorted_rows,

@@ -671,6 +671,10 @@ DECODE_NORM_FUSED = [os.environ.get("SVLA_DECODE_NORM_FUSED", "1") != "0"]
 # path's kernels (norm pair, then projection + lora_down + lora_up per projection: 15 launches) -- the A/B partner, the
 # second reference of the tests and the general fallback
 LORA_DECODE_KERNELS = [os.environ.get("SVLA_LORA_DECODE_KERNELS", "1") != "0"]
+# ... and, under enable_lora_decode(emb_head=True), embed the step's token with svla_lora_embed_decode and run the head
+# as svla_lora_gemv_down + svla_lora_head_gemv; SVLA_LORA_DECODE_EMB_HEAD_KERNELS=0 keeps the layers' GEMVs and takes
+# EmbedMergeLoRAFn / LMHeadCEFn at the two ends (tools/decode_bench.py times the two ends on their own with it)
+LORA_DECODE_EMB_HEAD_KERNELS = [os.environ.get("SVLA_LORA_DECODE_EMB_HEAD_KERNELS", "1") != "0"]
 
 
 def _lora_decode_ok(x_rows, k, weights, norm=False) -> bool:
@@ -2015,6 +2019,36 @@ class LMHeadCEFn(torch.autograd.Function):
         if dw is not None:
             K.linear_wgrad(dlog[:, :V], h.index_select(0, rows).contiguous(), [dw], accumulate=acc)
         return LMHeadCEFn._ret(ctx, dh, rw, rA, rB)
+
+
+def lm_head_lora_decode_ok(h: torch.Tensor, r: int) -> bool:
+    """Whether the decode head with an lm_head adapter runs as lm_head_lora_decode: no grad, M <= 8 rows, the decode
+    adapter kernels on (SVLA_LORA_DECODE_KERNELS) and a width svla_lora_head_gemv takes."""
+    return (not torch.is_grad_enabled() and LORA_DECODE_KERNELS[0] and LORA_DECODE_EMB_HEAD_KERNELS[0] and h.is_cuda
+            and K.lora_head_gemv_ok(h.shape[0], h.shape[1], r))
+
+
+def lm_head_lora_decode(h, w, target, cap, stash, scaling, r, A, B):
+    """LMHeadCEFn's forward for a decode step (M <= 8 rows, no grad) with the lm_head adapter attached, in the launch
+    count of the head without one: t = h A^T (svla_lora_gemv_down), then svla_lora_head_gemv streams lm_head once and
+    leaves the softcapped logits and the statistics, then svla_ce_finalize.  Returns (logits [M, V] view, loss)."""
+    h = _c(h)
+    M, V = h.shape[0], w.shape[0]
+    t = _empty(M, K.lora_R(r), like=h)
+    K.lora_gemv_down(h, [A], r, t)
+    logits_buf = _empty(M, K.round_up(V, 64), like=h)
+    ntn = K.ceil_div(V, 128)
+    stats = _empty(M, ntn, 3, dtype=F32, like=h)
+    K.lora_head_gemv(h, w, t, B, r, scaling, logits_buf, V, stats, cap)
+    lse = _empty(M, dtype=F32, like=h)
+    argmax = _empty(M, dtype=torch.int64, like=h)
+    loss_rows = _empty(M, dtype=F32, like=h)
+    loss2 = _empty(2, dtype=F32, like=h)
+    K.ce_finalize(V, ntn, stats, logits_buf[:, :V], target, lse, argmax, loss_rows, loss2)
+    stash["argmax"] = argmax
+    stash["lse"] = lse
+    stash["n_valid"] = loss2[1:2]
+    return logits_buf[:, :V], loss2[0]
 
 
 # ------------------------------------------------------------------------------------ attention plug-in

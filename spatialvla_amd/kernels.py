@@ -1178,6 +1178,33 @@ def lora_gemv(x: torch.Tensor, weights: List[torch.Tensor], t: torch.Tensor, mat
                                    _stream()), "svla_lora_gemv")
 
 
+LORA_HEAD_GEMV_MAX_K = 4096  # svla_lora_head_gemv keeps a weight row's whole K range per wave
+
+
+def lora_head_gemv_ok(M: int, K: int, r: int) -> bool:
+    """Whether svla_lora_head_gemv takes this decode-step lm_head: M <= 8 rows, K % 8 == 0 up to 4096."""
+    return 1 <= M <= LORA_GEMV_MAX_M and K % 8 == 0 and 8 <= K <= LORA_HEAD_GEMV_MAX_K and r % 8 == 0 and 8 <= r <= 64
+
+
+def lora_head_gemv(x: torch.Tensor, w: torch.Tensor, t: torch.Tensor, B: torch.Tensor, r: int, scaling: float,
+                   logits: torch.Tensor, N: int, row_stats: torch.Tensor, cap: float):
+    """Decode step's lm_head with an unmerged adapter, one pass over w [N, K]: logits[:, :N] = softcap(bf16(bf16(x w^T)
+    + bf16(scaling t B^T))) and row_stats [M, ceil(N/128), 3], bitwise lora_gemv + softcap_ce_rows (svla_lora_head_gemv);
+    t [M, >= r] from lora_gemv_down, B [N, r], M <= 8."""
+    for a, nm in ((x, "x"), (w, "w"), (t, "t"), (B, "B"), (logits, "logits")):
+        _chk_bf16(a, "lora_head_gemv " + nm)
+    M, K = x.shape
+    _req(tuple(w.shape) == (N, K) and w.stride(1) == 1 and tuple(B.shape) == (N, r) and B.stride(1) == 1,
+         f"lora_head_gemv: w [{N}, {K}] and B [{N}, {r}] with unit column stride")
+    _req(t.shape[0] == M and t.shape[1] >= r and logits.shape[0] == M and _ld(logits) >= N,
+         f"lora_head_gemv: t [{M}, >= {r}], logits [{M}, >= {N}]")
+    _req(row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == M * ceil_div(N, 128) * 3,
+         "lora_head_gemv: row_stats must be a contiguous fp32 [M, ceil(N/128), 3]")
+    L.check(L.lib().svla_lora_head_gemv(M, N, K, x.data_ptr(), _ld(x), w.data_ptr(), _ld(w), t.data_ptr(), _ld(t),
+                                        B.data_ptr(), _ld(B), int(r), float(scaling), float(cap), logits.data_ptr(),
+                                        _ld(logits), row_stats.data_ptr(), _stream()), "svla_lora_head_gemv")
+
+
 _lora_ws: dict = {}
 
 
@@ -1240,6 +1267,24 @@ def lora_embed_fwd(ids, img_index, embed, spatial, a0, A, B, r, scaling, normali
     L.check(L.lib().svla_lora_embed_fwd(rows, H, ids.data_ptr(), _ptr(img_index), embed.data_ptr(), spatial.data_ptr(),
                                         int(a0), na, A.data_ptr(), B.data_ptr(), int(r), float(scaling),
                                         float(normalizer), out.data_ptr(), _stream()), "svla_lora_embed_fwd")
+
+
+LORA_EMBED_DECODE_MAX_ROWS = 8
+
+
+def lora_embed_decode(ids, embed, spatial, a0, A, B, r, scaling, normalizer, out):
+    """Decode step (rows <= 8, no image slot): embed_merge and lora_embed_fwd in one launch, bitwise the two in sequence
+    (svla_lora_embed_decode)."""
+    rows, H = out.shape
+    na = spatial.shape[0]
+    _chk_bf16(out, "lora_embed_decode out")
+    _req(out.is_contiguous() and spatial.is_contiguous() and embed.is_contiguous() and ids.numel() == rows
+         and ids.dtype == torch.int64 and ids.is_contiguous(),
+         "lora_embed_decode: contiguous tables, one int64 id per output row")
+    _chk_embed_adapter(A, B, r, na, H, "lora_embed_decode")
+    L.check(L.lib().svla_lora_embed_decode(rows, H, ids.data_ptr(), embed.data_ptr(), spatial.data_ptr(), int(a0), na,
+                                           A.data_ptr(), B.data_ptr(), int(r), float(scaling), float(normalizer),
+                                           out.data_ptr(), _stream()), "svla_lora_embed_decode")
 
 
 def lora_embed_bwd(ids, sorted_rows, offsets, a0, na, dout, normalizer, A, B, r, scaling, dA, dB, accumulate=False):

@@ -589,5 +589,9 @@ class Gemma2ForCausalLM(nn.Module):
             raise ValueError("final_logit_softcapping must be set for the fused softcap/CE head")
         ad = getattr(self.lm_head, "lora", None)  # add_lora("spatialvla-linear+emb+h"): the adapter on lm_head
         adapter = () if ad is None else (ad.scaling, ad.r, ad.A, ad.B)
+        h2d = hidden_states.reshape(-1, hidden_states.shape[-1])
+        if ad is not None and Fn.lm_head_lora_decode_ok(h2d, ad.r):
+            # a decode step's rows under the adapter: T, one pass over lm_head (svla_lora_head_gemv), finalize
+            return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter)
         return Fn.LMHeadCEFn.apply(hidden_states.reshape(-1, hidden_states.shape[-1]), self.lm_head.weight, target,
                                    cap, stash, *adapter)

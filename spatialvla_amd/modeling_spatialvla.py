@@ -389,6 +389,17 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             # instead of past the end of the feature rows
             idx = torch.cumsum(img_mask.to(torch.int32), 0) - 1
             img_index = torch.where(img_mask & (idx < n_img), idx, -1).to(torch.int32)
+        ad = self._emb_adapter
+        if (ad is not None and image_features is None and ids.numel() <= K.LORA_EMBED_DECODE_MAX_ROWS
+                and not torch.is_grad_enabled() and self.lora_decode_emb_head and Fn.LORA_DECODE_KERNELS[0]
+                and Fn.LORA_DECODE_EMB_HEAD_KERNELS[0] and ids.is_cuda):
+            # a decode step under the Embedding adapter: nothing reads the CSR without a backward, and the merge and
+            # the adapter rows are one launch (svla_lora_embed_decode)
+            hidden = cfg.text_config.hidden_size
+            out = torch.empty(ids.numel(), hidden, dtype=embed_w.dtype, device=dev)
+            K.lora_embed_decode(ids, embed_w, self.spatial_embed_tokens.weight, int(cfg.action_token_begin_idx), ad.A,
+                                ad.B, ad.r, ad.scaling, float(torch.tensor(hidden ** 0.5, dtype=embed_w.dtype)), out)
+            return out.view(B, Lq, hidden)
         spatial_w, sort_rows, offsets, a0 = None, None, None, 0
         if cfg.use_spatial_token:
             spatial_w = self.spatial_embed_tokens.weight
@@ -750,7 +761,13 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
     def lora_decode(self) -> bool:
         return bool(self.language_model.model.lora_decode)
 
-    def enable_lora_decode(self, enabled: bool = True):
+    @property
+    def lora_decode_emb_head(self) -> bool:
+        """Whether the unmerged decode also permits an adapter on spatial_embed_tokens / lm_head
+        (enable_lora_decode(True, emb_head=True))."""
+        return bool(self.__dict__.get("_svla_lora_decode_emb_head", False))
+
+    def enable_lora_decode(self, enabled: bool = True, emb_head: bool = False):
         """Run predict_action, generate, forward(past_key_values=...) and forward(use_cache=True) with unmerged LoRA
         adapters attached (mid-training evaluation, a base model with a swappable adapter from load_lora): the prefill
         on the training forward's rank-r kernels, every decode-step projection as svla_lora_gemv_down + svla_lora_gemv
@@ -760,30 +777,43 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         With the "spatialvla-linear" set the prefill's SigLIP / Ego3D / projector run through their LoRA Functions under
         no_grad, inside the captured prefill graph; the decode steps never touch the vision side.  A modules_to_save
         spatial table needs nothing special (the graphs read the table in place).  With an adapter on
-        spatial_embed_tokens or lm_head ("spatialvla-linear+emb", "+emb+h") the unmerged decode is not built: turning
-        the switch on raises NotImplementedError, before any state changes -- merge_lora() first."""
-        if enabled:
-            self._refuse_emb_head_decode("enable_lora_decode")
+        spatial_embed_tokens or lm_head ("spatialvla-linear+emb", "+emb+h") the unmerged decode is a second opt-in:
+        without emb_head=True turning the switch on raises NotImplementedError, before any state changes (merge_lora()
+        first, or pass emb_head=True).  emb_head=True turns the switch on and permits those two adapters: the prefill
+        keeps EmbedMergeLoRAFn / LMHeadCEFn under no_grad inside its graph, a decode step embeds its token with
+        svla_lora_embed_decode and runs the head as svla_lora_gemv_down + svla_lora_head_gemv + svla_ce_finalize
+        (DESIGN.md section 4 "LoRA on both ends"); the graphs read those A and B in place as well.
+        enable_lora_decode(False) clears both."""
+        permit = bool(enabled) and bool(emb_head)
+        if enabled and not permit:
+            self._refuse_emb_head_decode("enable_lora_decode", permitted=False)
         self.language_model.enable_lora_decode(enabled)
+        self.__dict__["_svla_lora_decode_emb_head"] = permit
         self.clear_decode_cache()
 
     def _adapter_key(self):
         """What the captured decode graphs bake in about the adapters: the switch, the first adapter's storage, its
         rank and scaling, and the storage of the projector's adapter when the vision side carries adapters (the prefill
-        graph runs SigLIP, Ego3D and the projector with theirs; they are attached and rebound together) -- None without
-        adapters."""
+        graph runs SigLIP, Ego3D and the projector with theirs; they are attached and rebound together), then the
+        storage of the Embedding adapter and of the lm_head adapter when attached (the step graphs read them) -- None
+        without adapters."""
         ad = getattr(self.language_model.model.layers[0].self_attn.q_proj, "lora", None)
         if ad is None:
             return None
-        vis = getattr(self.multi_modal_projector.linear, "lora", None)
         key = (self.lora_decode, ad.A.data_ptr(), ad.r, ad.scaling)
-        return key + (vis.A.data_ptr(),) if vis is not None else key
+        for extra in (getattr(self.multi_modal_projector.linear, "lora", None), self._emb_adapter, self._head_adapter):
+            if extra is not None:
+                key += (extra.A.data_ptr(),)
+        return key
 
-    def _refuse_emb_head_decode(self, what: str):
-        if self._emb_adapter is not None or self._head_adapter is not None:
+    def _refuse_emb_head_decode(self, what: str, permitted: Optional[bool] = None):
+        if permitted is None:
+            permitted = self.lora_decode_emb_head
+        if not permitted and (self._emb_adapter is not None or self._head_adapter is not None):
             raise NotImplementedError(f"{what}: the KV-cached decode with an unmerged adapter on spatial_embed_tokens or "
-                                      f"lm_head (the {self.lora_targets!r} set) is not built: call merge_lora() first "
-                                      "(forward without a cache and predict_action_uncached run unmerged)")
+                                      f"lm_head (the {self.lora_targets!r} set) is a separate opt-in: call merge_lora() "
+                                      "first, or enable_lora_decode(True, emb_head=True) (forward without a cache and "
+                                      "predict_action_uncached run unmerged)")
 
     def _require_merged(self, what: str):
         self._refuse_emb_head_decode(what)

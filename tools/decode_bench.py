@@ -35,7 +35,11 @@ def lora_main(args):
     """--lora R: ms per decode token (and prefill + first token) of three variants in one process, three alternating
     rounds: the adapters merged into the weights (the base path), unmerged on svla_lora_gemv_down / svla_lora_gemv
     (enable_lora_decode), and unmerged composed from the training-path kernels (SVLA_LORA_DECODE_KERNELS=0).  One model
-    per variant, each warmed up (and its graphs captured) under its own setting, so the rounds only replay."""
+    per variant, each warmed up (and its graphs captured) under its own setting, so the rounds only replay.
+    --lora-targets spatialvla-linear+emb / +emb+h: the same three with the Embedding (and lm_head) adapter attached
+    (enable_lora_decode(True, emb_head=True): svla_lora_embed_decode / svla_lora_head_gemv at the two ends), and the
+    variant adapters_kernels_ends_composed (SVLA_LORA_DECODE_EMB_HEAD_KERNELS=0: the layers' GEMVs kept, the two ends
+    composed), which isolates the two new kernels."""
     from bench import build_model, make_batch
     from spatialvla_amd import functional as Fn, presets
     dev = torch.device("cuda:0")
@@ -44,24 +48,35 @@ def lora_main(args):
     P = int((b["token_type_ids"][0] == 0).sum())
     inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
     n_long = args.new_tokens + args.long
+    ends = "+emb" in args.lora_targets
+    variants = args.variants.split(",")
+    if ends and args.variants == VARIANTS:
+        variants.append("adapters_kernels_ends_composed")
     models, toks = {}, {}
-    for name in args.variants.split(","):
+    for name in variants:
         m = build_model(cfgd, dev).eval()
-        m.add_lora(args.lora, float(args.lora), seed=1)
+        m.add_lora(args.lora, float(args.lora), target_modules=args.lora_targets, seed=1)
         gen = torch.Generator(device="cpu").manual_seed(2)
         with torch.no_grad():
             for _, lin in m._lora_linears():  # a trained adapter: B away from its zero initialisation
                 lin.lora.B.copy_((torch.randn(lin.lora.B.shape, generator=gen) * 0.01).to(torch.bfloat16))
+            if ends:  # the Embedding adapter starts at A = 0, the lm_head adapter at B = 0
+                ad = m.spatial_embed_tokens.lora
+                ad.A.copy_((torch.randn(ad.A.shape, generator=gen) * 0.01).to(torch.bfloat16))
+                ad = getattr(m.language_model.lm_head, "lora", None)
+                if ad is not None:
+                    ad.B.copy_((torch.randn(ad.B.shape, generator=gen) * 0.01).to(torch.bfloat16))
         if name == "merged":
             m.merge_lora()
         else:
-            m.enable_lora_decode()
+            m.enable_lora_decode(True, emb_head=ends)
         Fn.LORA_DECODE_KERNELS[0] = name != "adapters_composed"
+        Fn.LORA_DECODE_EMB_HEAD_KERNELS[0] = name != "adapters_kernels_ends_composed"
         with torch.no_grad():  # warm-up under the variant's setting: every graph this model replays is captured here
             m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1)
             toks[name] = m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1)
         models[name] = m
-    Fn.LORA_DECODE_KERNELS[0] = True
+    Fn.LORA_DECODE_KERNELS[0] = Fn.LORA_DECODE_EMB_HEAD_KERNELS[0] = True
     rounds = []
     with torch.no_grad():
         for _ in range(args.rounds):
@@ -75,12 +90,20 @@ def lora_main(args):
     per = {n: [r[n]["ms_per_decode_token"] for r in rounds] for n in models}
     print(json.dumps({
         "metric": "SpatialVLA-4B greedy decode latency with LoRA adapters", "unit": "ms", "batch": args.batch, "r": args.lora,
+        "lora_targets": args.lora_targets,
         "prompt_tokens": P, "decode_tokens_timed": n_long - 1, "rounds": rounds,
         "ms_per_decode_token_min_max": {n: [min(v), max(v)] for n, v in per.items()},
         "kernels_tokens_equal_composed": (bool(torch.equal(toks["adapters_kernels"], toks["adapters_composed"]))
                                           if "adapters_kernels" in toks and "adapters_composed" in toks else None),
+        "kernels_tokens_equal_ends_composed": (bool(torch.equal(toks["adapters_kernels"],
+                                                                toks["adapters_kernels_ends_composed"]))
+                                               if "adapters_kernels_ends_composed" in toks and "adapters_kernels" in toks
+                                               else None),
         "decode_graphs": bool(next(iter(models.values())).decode_graphs), "dtype": "bf16",
         "data": "synthetic OXE-shaped prompt, random-init weights and adapters"}), flush=True)
+
+
+VARIANTS = "merged,adapters_kernels,adapters_composed"
 
 
 def main():
@@ -92,8 +115,12 @@ def main():
     ap.add_argument("--no-uncached", action="store_true")
     ap.add_argument("--lora", type=int, default=0, metavar="R",
                     help="rank-R adapters: merged vs unmerged (adapter GEMVs) vs unmerged (composed), three rounds")
-    ap.add_argument("--variants", default="merged,adapters_kernels,adapters_composed",
-                    help="--lora: which of merged, adapters_kernels, adapters_composed to run (a kernel trace takes one)")
+    ap.add_argument("--lora-targets", default="gemma2-linear",
+                    help="--lora: the target set (gemma2-linear, spatialvla-linear, spatialvla-linear+emb, "
+                         "spatialvla-linear+emb+h)")
+    ap.add_argument("--variants", default=VARIANTS,
+                    help="--lora: which of merged, adapters_kernels, adapters_composed (with an +emb set also "
+                         "adapters_kernels_ends_composed, added by default) to run (a kernel trace takes one)")
     ap.add_argument("--rounds", type=int, default=3, help="--lora: alternating rounds")
     args = ap.parse_args()
     if args.lora:
