@@ -352,6 +352,51 @@ int svla_lora_softcap_ce_rows(int64_t M, int64_t N, void* logits, int64_t ld, co
                               int32_t r, float scaling, float cap, float* row_stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weight-only MX fp8 decode (csrc/fp8_decode.hip): the decode step's projections (M <= 8 token rows, the KV-cached
+ * step of model/modeling_spatialvla.py:440-492) of Gemma2 q|k|v, o, gate|up and down (model/modeling_gemma2.py:86-92,
+ * 351-354) and lm_head + final softcap (:993-997) on e4m3 copies of the weights -- the values and exponents of
+ * svla_quant_mx_rows(W), dequantised in registers; x stays bf16 and the accumulation fp32, so a token streams half the
+ * weight bytes.  The house rules hold: fp32 in a fixed order, no float atomics, no block waits on another, no allocation
+ * or host sync (graph-capturable), bitwise stable run to run.
+ * ---------------------------------------------------------------------------------------- */
+/* The exponent bytes of svla_quant_mx_rows' tile-major `scales` (rows, K, sld as there) repacked row-major for the
+ * GEMVs: out[r * ldo + b] = the E8M0 byte of block b (k in [32 b, 32 b + 32)) of row r, b < K / 32 -- the bytes a GEMV
+ * lane needs sit beside the row it streams.  ldo % 4 == 0, ldo >= K / 32; scales and out 4-B aligned; bytes
+ * K / 32 .. ldo - 1 of a row are not written. */
+int svla_mx_scales_rowmajor(int64_t rows, int64_t K, const void* scales, int64_t sld, void* out, int64_t ldo,
+                            void* stream);
+/* A weight W [N][K] as up to 3 row segments (q|k|v, or gate|up): segment s covers rows [start[s], start[s+1]),
+ * start[0] = 0, start[nseg] = N; q[s] its e4m3 bytes [N_s][ldq] (16-B aligned, ldq % 16 == 0) and x[s] its exponent
+ * bytes [N_s][lds] in svla_mx_scales_rowmajor's layout (lds >= K / 32). */
+typedef struct {
+  const void* q[3];
+  const void* x[3];
+  int64_t start[4];
+  int64_t ldq;
+  int64_t lds;
+  int32_t nseg;
+  int32_t _pad;
+} svla_mxfp8_rows;
+/* y[m,n] = bf16( sum_b 2^X(n,b) sum_{k in b} x[m,k] q[n,k] ) for M <= 8 rows of bf16 x [M][ldx] (ldx % 8 == 0), any
+ * N >= 1, K % 128 == 0.  Epilogues (epi->kind): SVLA_EPI_STORE (c [M][N]); SVLA_EPI_GEGLU (N = 2 I, two segments of I
+ * rows: gate, up): g and u go to epi->out1 / out2 and c [M][I] = bf16(bf16(gelu_tanh(g)) u), SVLA_EPI_GEGLU's element
+ * formula and table.  norm != NULL (K <= 2560; x is then not read and may be NULL): the norm pair of
+ * svla_gemv_rmsnorm2 runs in the prologue, h_out = bf16(res + bf16(rms(y; w1))) stored and bitwise
+ * svla_add_rmsnorm2_fwd, and the product is taken with x = bf16(rms(h_out; w2)).  STORE with K > 4096 (the down
+ * projection) splits a row's K range over the four waves of a block and adds the partial sums in wave order.  A block
+ * whose exponent byte is 0xFF (the quantiser's NaN block) makes the output NaN; an all-zero block contributes exactly 0. */
+int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_lora_norm2* norm,
+                    const svla_mxfp8_rows* W, void* c, int64_t ldc, const svla_epilogue* epi, void* stream);
+/* The decode head in one pass over the e4m3 lm_head (q [N][ldq], exponents xs [N][lds], one segment): the product of
+ * svla_gemv_mxfp8 (STORE, bit for bit for the same K), then logits[m][n] = bf16(cap tanh(bf16(bf16(y) / cap)))
+ * ([M][ld], ld % 8 == 0, ld >= N; columns >= N are not written) and row_stats [M][ceil(N/128)][3] = {max, sum exp,
+ * first argmax} of every 128-column group in svla_softcap_ce_rows' partition and combine order -- bitwise that function
+ * applied to y, so svla_ce_finalize follows unchanged.  M <= 8, any N >= 1, K % 128 == 0, K <= 4096. */
+int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q, int64_t ldq,
+                         const void* xs, int64_t lds, float cap, void* logits, int64_t ld, float* row_stats,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via
  * GEMMA2_ATTENTION_FUNCTION (:317-322) with the prefix-LM additive mask of
  * _update_causal_mask (model/modeling_spatialvla.py:258-306) and Gemma2 RoPE

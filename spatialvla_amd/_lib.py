@@ -81,6 +81,11 @@ class LoraNorm2(ctypes.Structure):
                 ("eps1", c_f32), ("eps2", c_f32)]
 
 
+class MxFp8Rows(ctypes.Structure):
+    _fields_ = [("q", c_vp * 3), ("x", c_vp * 3), ("start", c_i64 * 4), ("ldq", c_i64), ("lds", c_i64),
+                ("nseg", c_i32), ("_pad", c_i32)]
+
+
 LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
 LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU, LORA_EPI_GELU, LORA_EPI_RESID, LORA_EPI_SCALE = 0, 1, 2, 3, 4, 5
 
@@ -127,6 +132,11 @@ SIGNATURES = {
                                     c_vp, c_vp, c_i32, c_vp]),
     "svla_lora_softcap_ce_rows": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_f32, c_f32, c_vp,
                                           c_vp]),
+    "svla_mx_scales_rowmajor": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "svla_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(LoraNorm2), ctypes.POINTER(MxFp8Rows),
+                                c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
+    "svla_head_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_i64,
+                                     c_vp, c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

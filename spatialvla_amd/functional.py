@@ -504,6 +504,49 @@ class FP8Weights:
         return o
 
 
+class FP8DecodeWeights:
+    """Weight-only OCP MX e4m3 copies for the KV-cached decode step (enable_fp8_decode): of one Gemma2 layer's q|k|v
+    [4096, H], o [H, 2048], gate|up [2I, H] and down [H, I], or of lm_head [V, H].  A copy is svla_quant_mx_rows(W) --
+    the tested quantiser defines the numbers -- with the exponents repacked row-major (svla_mx_scales_rowmajor), the
+    layout the GEMVs of csrc/fp8_decode.hip read.  Built lazily by the first fp8 decode step and rebuilt when a weight
+    moved, was modified in place (tensor version), or the optimizer stepped (WEIGHT_EPOCH).  `builds` counts this
+    holder's (re)builds: the captured decode graphs hold raw pointers into the copies, so the decode state compares the
+    model's sum of them (SpatialVLAForConditionalGeneration._fp8_decode_key); BUILDS counts those of every holder
+    (tests, tools)."""
+
+    BUILDS = [0]
+
+    def __init__(self):
+        self.mats = {}
+        self.builds = 0
+
+    def get(self, name, mats):
+        """([q segments e4m3 [N_i, K]], [exponent segments uint8 [N_i, K/32]]) of cat(mats, 0): one segment, or for
+        name == "gate_up" the gate rows and the up rows (the GEGLU pair)."""
+        key = (WEIGHT_EPOCH[0],) + tuple((m.data_ptr(), m._version) for m in mats)
+        hit = self.mats.get(name)
+        if hit is None or hit["key"] != key:
+            q, sc = K.quant_mx_rows(FP8Weights._rows(mats))
+            s = K.mx_scales_rowmajor(sc)
+            if name == "gate_up":
+                I = mats[0].shape[0]
+                qs, ss = [q[:I], q[I:]], [s[:I], s[I:]]
+            else:
+                qs, ss = [q], [s]
+            hit = self.mats[name] = {"key": key, "q": qs, "s": ss}
+            self.builds += 1
+            FP8DecodeWeights.BUILDS[0] += 1
+        return hit["q"], hit["s"]
+
+    def nbytes(self) -> int:
+        return sum(t.numel() for e in self.mats.values() for t in e["q"] + e["s"])
+
+
+def fp8_decode_ok(M: int, k: int, weights, norm: bool = False) -> bool:
+    """Whether a decode-step projection runs on its e4m3 copy: shapes svla_gemv_mxfp8 takes (else the bf16 path)."""
+    return all(w.dim() == 2 and w.shape[1] == k for w in weights) and K.gemv_mxfp8_ok(M, k, norm)
+
+
 def _fp8_linear(x, f8, name, mats, out, x_mx=None, **kw):
     """out = epi(x @ cat(mats)^T) with both operands quantised to e4m3 (x per call -- or x_mx, the MX copy x's
     producer already made -- weights cached)."""
@@ -746,14 +789,16 @@ def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
 
 @torch.no_grad()
 def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg: GemmaAttnCfg,
-                           pre=None, skip_o=False, lora=None):
+                           pre=None, skip_o=False, lora=None, f8d=None):
     """Gemma2Attention.forward with a KV cache (modeling_gemma2.py:364-413, cache update :387-395), inference
     only.  x holds the cfg.L new tokens of each of the cfg.B sequences, at absolute positions p0 .. p0+L-1;
     their rotated k and v are written into rows p0.. of k_cache/v_cache ([B, capacity, Hkv*D]).  The prefill
     (p0 == 0) runs the flash kernel of the uncached forward over the prompt, so it is bit-identical to it;
     later steps run the decode kernel over the first p0+L cache rows.  pre = (res, y, w1, w2, eps1, eps2, h_out): a
     decode step whose input x = rms(res + rms(y; w1); w2) is formed inside the q|k|v GEMV (h_out the new residual).
-    lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections."""
+    lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections.
+    f8d: the layer's FP8DecodeWeights (enable_fp8_decode) -- a decode step (p0 > 0) then streams the e4m3 copies of
+    q|k|v and o (svla_gemv_mxfp8); the prefill never reads them, and shapes the kernel refuses keep the bf16 GEMV."""
     if lora is not None:
         # the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term needs T
         # complete before the projection starts, which inside one launch would take a grid barrier
@@ -776,7 +821,9 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
         # the kernels read table row b*Lq+t (per-sequence positions), so a shared table is repeated per sequence
         if cos.shape[0] != B * Lq:
             cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
-        if pre is not None:
+        if f8d is not None and fp8_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
+            K.gemv_mxfp8(x, *f8d.get("qkv", [wq, wk, wv]), qkv, norm=pre)
+        elif pre is not None:
             K.gemv_rmsnorm2(*pre, [wq, wk, wv], qkv)
         else:
             K.linear_fwd(x, [wq, wk, wv], qkv)
@@ -807,7 +854,10 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     if skip_o:  # the caller runs the o projection (gemma_mlp_decode with o=(attn, wo): inside its launch)
         return attn
     out = _empty(M, wo.shape[0], like=like)
-    K.linear_fwd(attn, [wo], out)
+    if p0 > 0 and f8d is not None and fp8_decode_ok(M, qd, [wo]):
+        K.gemv_mxfp8(attn, *f8d.get("o", [wo]), out)
+    else:
+        K.linear_fwd(attn, [wo], out)
     return out
 
 
@@ -833,11 +883,23 @@ DECODE_MLP_PERSIST = [os.environ.get("SVLA_DECODE_MLP_PERSIST", "1") != "0"]
 
 
 @torch.no_grad()
-def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora=None):
+def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora=None, f8d=None):
     """Decode-step Gemma2 MLP (modeling_gemma2.py:91-92) whose input is the post-attention + pre-feedforward norm pair
     (:487-490), formed inside the gate|up GEMV: h_out = res + rms(y; w1) (the residual stream), returns
     down(gelu_tanh(gate x) * up x) with x = rms(h_out; w2).
-    lora = (r, scaling, (Ag, Bg), (Au, Bu), (Ad, Bd)): unmerged adapters on the three projections."""
+    lora = (r, scaling, (Ag, Bg), (Au, Bu), (Ad, Bd)): unmerged adapters on the three projections.
+    f8d: the layer's FP8DecodeWeights (enable_fp8_decode): the two-launch form on the e4m3 copies -- the norm-prologue
+    gate|up GeGLU GEMV, then the (split-K) down GEMV, both svla_gemv_mxfp8; not combined with `o` or `lora`."""
+    if f8d is not None and lora is None and o is None:
+        M, H = y.shape
+        I = wg.shape[0]
+        if fp8_decode_ok(M, H, [wg, wu], norm=True) and fp8_decode_ok(M, I, [wd]) and wu.shape[0] == I:
+            hact, g, u = (_empty(M, I, like=y) for _ in range(3))
+            K.gemv_mxfp8(None, *f8d.get("gate_up", [wg, wu]), hact, geglu_out=(g, u),
+                         norm=(res, y, w1, w2, eps1, eps2, h_out))
+            out = _empty(M, wd.shape[0], like=y)
+            K.gemv_mxfp8(hact, *f8d.get("down", [wd]), out)
+            return out
     if lora is not None:
         # With adapters neither the persistent svla_decode_mlp nor DECODE_O_FUSED is used: each adapter term needs T
         # (a reduction over the whole input row) complete between the rank-r GEMV and the projection that adds it,
@@ -2019,6 +2081,33 @@ class LMHeadCEFn(torch.autograd.Function):
         if dw is not None:
             K.linear_wgrad(dlog[:, :V], h.index_select(0, rows).contiguous(), [dw], accumulate=acc)
         return LMHeadCEFn._ret(ctx, dh, rw, rA, rB)
+
+
+def lm_head_fp8_decode_ok(h: torch.Tensor) -> bool:
+    """Whether the decode head runs on the e4m3 lm_head: no grad, M <= 8 rows and a width svla_head_gemv_mxfp8 takes."""
+    return not torch.is_grad_enabled() and h.is_cuda and K.head_gemv_mxfp8_ok(h.shape[0], h.shape[1])
+
+
+def lm_head_fp8_decode(h, w, target, cap, stash, f8d: FP8DecodeWeights):
+    """LMHeadCEFn's forward for a decode step (M <= 8 rows, no grad) on the e4m3 copy of lm_head: svla_head_gemv_mxfp8
+    streams the copy once and leaves the softcapped logits and the statistics, then svla_ce_finalize.  Returns
+    (logits [M, V] view, loss)."""
+    h = _c(h)
+    M, V = h.shape[0], w.shape[0]
+    (wq,), (ws,) = f8d.get("lm_head", [w])
+    logits_buf = _empty(M, K.round_up(V, 64), like=h)
+    ntn = K.ceil_div(V, 128)
+    stats = _empty(M, ntn, 3, dtype=F32, like=h)
+    K.head_gemv_mxfp8(h, wq, ws, logits_buf, V, stats, cap)
+    lse = _empty(M, dtype=F32, like=h)
+    argmax = _empty(M, dtype=torch.int64, like=h)
+    loss_rows = _empty(M, dtype=F32, like=h)
+    loss2 = _empty(2, dtype=F32, like=h)
+    K.ce_finalize(V, ntn, stats, logits_buf[:, :V], target, lse, argmax, loss_rows, loss2)
+    stash["argmax"] = argmax
+    stash["lse"] = lse
+    stash["n_valid"] = loss2[1:2]
+    return logits_buf[:, :V], loss2[0]
 
 
 def lm_head_lora_decode_ok(h: torch.Tensor, r: int) -> bool:

@@ -1205,6 +1205,109 @@ def lora_head_gemv(x: torch.Tensor, w: torch.Tensor, t: torch.Tensor, B: torch.T
                                         _ld(logits), row_stats.data_ptr(), _stream()), "svla_lora_head_gemv")
 
 
+# ------------------------------------------------------------------------- weight-only MX fp8 decode (fp8_decode.hip)
+GEMV_MXFP8_MAX_M = 8          # token rows of svla_gemv_mxfp8 / svla_head_gemv_mxfp8
+HEAD_GEMV_MXFP8_MAX_K = 4096  # svla_head_gemv_mxfp8 keeps a weight row's whole K range per wave
+
+
+def gemv_mxfp8_ok(M: int, K: int, norm: bool = False) -> bool:
+    """Whether svla_gemv_mxfp8 takes this decode-step projection: M <= 8 rows, K % 128 == 0 (the norm prologue:
+    K <= GEMV_NORM_MAX_K)."""
+    return 1 <= M <= GEMV_MXFP8_MAX_M and K >= 128 and K % 128 == 0 and (not norm or K <= GEMV_NORM_MAX_K)
+
+
+def head_gemv_mxfp8_ok(M: int, K: int) -> bool:
+    return 1 <= M <= GEMV_MXFP8_MAX_M and K % 128 == 0 and 128 <= K <= HEAD_GEMV_MXFP8_MAX_K
+
+
+def mx_scales_rowmajor(sc: MXScales, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The exponent bytes of an MXScales (tile-major) as a row-major uint8 [rows, K/32] matrix, byte (r, b) = 127 + X of
+    block b of row r (svla_mx_scales_rowmajor): the layout the fp8 decode GEMVs read beside their weight rows."""
+    rows, Kd = sc.rows, sc.K
+    if out is None:
+        out = torch.empty(rows, Kd // 32, dtype=torch.uint8, device=sc.buf.device)
+    _req(out.dtype == torch.uint8 and tuple(out.shape) == (rows, Kd // 32) and out.stride(1) == 1
+         and out.stride(0) % 4 == 0, f"mx_scales_rowmajor: out must be uint8 [{rows}, {Kd // 32}] with a row stride % 4 == 0")
+    L.check(L.lib().svla_mx_scales_rowmajor(rows, Kd, sc.buf.data_ptr(), sc.ld, out.data_ptr(), out.stride(0),
+                                            _stream()), "svla_mx_scales_rowmajor")
+    return out
+
+
+def _mxfp8_rows(wq: Sequence[torch.Tensor], ws: Sequence[torch.Tensor], K: int, what: str):
+    _req(1 <= len(wq) <= 3 and len(wq) == len(ws), f"{what}: 1..3 weight segments, one exponent matrix each")
+    W = L.MxFp8Rows()
+    n = 0
+    for i, (q, s) in enumerate(zip(wq, ws)):
+        _req(q.is_cuda and q.dtype == FP8 and q.dim() == 2 and q.shape[1] == K and q.stride(1) == 1
+             and q.stride(0) == wq[0].stride(0), f"{what}: segment {i} must be e4m3 [N_i, {K}] rows of one stride")
+        _req(s.dtype == torch.uint8 and s.dim() == 2 and tuple(s.shape) == (q.shape[0], K // 32) and s.stride(1) == 1
+             and s.stride(0) == ws[0].stride(0), f"{what}: segment {i} exponents must be uint8 [N_i, {K // 32}]")
+        W.q[i], W.x[i], W.start[i] = q.data_ptr(), s.data_ptr(), n
+        n += q.shape[0]
+    W.start[len(wq)] = n
+    W.ldq, W.lds, W.nseg = wq[0].stride(0), ws[0].stride(0), len(wq)
+    return W, n
+
+
+def gemv_mxfp8(x: Optional[torch.Tensor], wq: Sequence[torch.Tensor], ws: Sequence[torch.Tensor], out: torch.Tensor,
+               geglu_out=None, norm=None):
+    """Decode step on weight-only MX fp8: out = bf16(sum_b 2^X sum_{k in b} x q) over the row segments wq (e4m3 [N_i, K])
+    with exponents ws (uint8 [N_i, K/32], mx_scales_rowmajor), M <= 8, K % 128 == 0 (svla_gemv_mxfp8).  geglu_out =
+    (g, u) with wq = [gate, up]: g, u stored there and out = bf16(bf16(gelu_tanh(g)) u).  norm = (res, y, w1, w2, eps1,
+    eps2, h_out): x is not read -- h_out = bf16(res + rms(y; w1)) is stored and the product uses x = rms(h_out; w2)
+    (svla_add_rmsnorm2_fwd, bitwise), K <= GEMV_NORM_MAX_K."""
+    _chk_bf16(out, "gemv_mxfp8 out")
+    nrm = None
+    if norm is not None:
+        res, y, w1, w2, eps1, eps2, h_out = norm
+        for a, nm in ((res, "res"), (y, "y"), (h_out, "h_out"), (w1, "w1"), (w2, "w2")):
+            _chk_bf16(a, "gemv_mxfp8 " + nm)
+        M, K = y.shape
+        _req(res.shape == y.shape == h_out.shape and _ld(res) == _ld(y) == _ld(h_out), "gemv_mxfp8: res/y/h_out rows")
+        _req(w1.numel() == K and w2.numel() == K, "gemv_mxfp8: norm weights")
+        nrm = L.LoraNorm2()
+        nrm.res, nrm.y, nrm.w1, nrm.w2, nrm.h_out = (a.data_ptr() for a in (res, y, w1, w2, h_out))
+        nrm.ld, nrm.eps1, nrm.eps2 = _ld(y), float(eps1), float(eps2)
+    else:
+        _chk_bf16(x, "gemv_mxfp8 x")
+        M, K = x.shape
+    W, N = _mxfp8_rows(wq, ws, K, "gemv_mxfp8")
+    if geglu_out is not None:
+        _req(len(wq) == 2 and wq[0].shape[0] == wq[1].shape[0], "gemv_mxfp8: GEGLU takes [gate, up]")
+        I = wq[0].shape[0]
+        for a in geglu_out:
+            _chk_bf16(a, "gemv_mxfp8 g/u")
+            _req(a.shape[0] >= M and a.shape[1] >= I, "gemv_mxfp8: g/u shape")
+        _req(out.shape[0] >= M and out.shape[1] >= I, "gemv_mxfp8: out shape")
+        e = _epi(L.EPI_GEGLU, out1=geglu_out[0], out2=geglu_out[1])
+    else:
+        _req(out.shape[0] >= M and out.shape[1] >= N, "gemv_mxfp8: out shape")
+        e = _epi(L.EPI_STORE)
+    L.check(L.lib().svla_gemv_mxfp8(M, N, K, _ptr(x) if norm is None else None, _ld(x) if norm is None else 0,
+                                    ctypes.byref(nrm) if nrm is not None else None, ctypes.byref(W), out.data_ptr(),
+                                    _ld(out), ctypes.byref(e), _stream()), "svla_gemv_mxfp8")
+
+
+def head_gemv_mxfp8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, logits: torch.Tensor, N: int,
+                    row_stats: torch.Tensor, cap: float):
+    """The decode head on the e4m3 lm_head, one pass over wq [N, K] (exponents ws [N, K/32]): logits[:, :N] =
+    softcap(bf16(product)) and row_stats [M, ceil(N/128), 3], bitwise gemv_mxfp8 + softcap_ce_rows
+    (svla_head_gemv_mxfp8); M <= 8, K % 128 == 0, K <= 4096."""
+    _chk_bf16(x, "head_gemv_mxfp8 x")
+    _chk_bf16(logits, "head_gemv_mxfp8 logits")
+    M, K = x.shape
+    _req(wq.is_cuda and wq.dtype == FP8 and tuple(wq.shape) == (N, K) and wq.stride(1) == 1,
+         f"head_gemv_mxfp8: wq must be e4m3 [{N}, {K}]")
+    _req(ws.dtype == torch.uint8 and tuple(ws.shape) == (N, K // 32) and ws.stride(1) == 1,
+         f"head_gemv_mxfp8: ws must be uint8 [{N}, {K // 32}]")
+    _req(logits.shape[0] == M and _ld(logits) >= N, f"head_gemv_mxfp8: logits [{M}, >= {N}]")
+    _req(row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == M * ceil_div(N, 128) * 3,
+         "head_gemv_mxfp8: row_stats must be a contiguous fp32 [M, ceil(N/128), 3]")
+    L.check(L.lib().svla_head_gemv_mxfp8(M, N, K, x.data_ptr(), _ld(x), wq.data_ptr(), wq.stride(0), ws.data_ptr(),
+                                         ws.stride(0), float(cap), logits.data_ptr(), _ld(logits),
+                                         row_stats.data_ptr(), _stream()), "svla_head_gemv_mxfp8")
+
+
 _lora_ws: dict = {}
 
 

@@ -385,6 +385,17 @@ class Gemma2Model(nn.Module):
         for layer in self.layers:
             layer.self_attn._svla_lora_decode = self.lora_decode
 
+    def enable_fp8_decode(self, enabled: bool = True):
+        """Weight-only MX fp8 decode (opt-in): the fused decode step (_decode_fused: cache position > 0, <= 8 new token
+        rows) streams e4m3 copies of q|k|v, o, gate|up and down (Fn.FP8DecodeWeights, one holder per layer, built by the
+        first such step) through svla_gemv_mxfp8.  The prefill and every other forward keep the bf16 weights."""
+        for layer in self.layers:
+            layer._svla_fp8_decode = Fn.FP8DecodeWeights() if enabled else None
+
+    @property
+    def fp8_decode(self) -> bool:
+        return getattr(self.layers[0], "_svla_fp8_decode", None) is not None
+
     def get_input_embeddings(self):
         return self.embed_tokens
 
@@ -453,7 +464,7 @@ class Gemma2Model(nn.Module):
         res = hidden.reshape(-1, H).contiguous()
         if (Fn.DECODE_NORM_FUSED[0] and cache.seen_tokens > 0 and res.shape[0] <= 8
                 and H <= Kn.GEMV_NORM_MAX_K and H % 8 == 0
-                and all(getattr(l.mlp, "_svla_fp8", None) is None for l in layers)):
+                and (self.fp8_decode or all(getattr(l.mlp, "_svla_fp8", None) is None for l in layers))):
             return self._decode_fused(res, shp, rope, cache)
         x = layers[0].input_layernorm(res)
         for i, layer in enumerate(layers):
@@ -489,17 +500,19 @@ class Gemma2Model(nn.Module):
                 pre = (h, m, po.weight, layer.input_layernorm.weight, po.eps, layer.input_layernorm.eps, res)
             la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))
             lm = _lora_args(_lora_of(mlp.gate_proj, mlp.up_proj, mlp.down_proj))
+            # weight-only fp8 decode (enable_fp8_decode): the layer's e4m3 copies, never together with adapters
+            f8d = getattr(layer, "_svla_fp8_decode", None) if la is None and lm is None else None
             # o projection inside the MLP's launch (never with adapters: their term needs its own launch boundary)
-            fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None
+            fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None and f8d is None
             a = Fn.gemma_attention_cached(x if i == 0 else None, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight,
                                           at.o_proj.weight, cos, sin, cache.key_cache[i], cache.value_cache[i],
                                           cache.kv_class, cache.seen_tokens, at.attn_cfg(B, Lq), pre=pre,
-                                          skip_o=fuse_o, lora=la)
+                                          skip_o=fuse_o, lora=la, f8d=f8d)
             pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
             h = torch.empty_like(res)
             m = Fn.gemma_mlp_decode(res, None if fuse_o else a, pa.weight, pf.weight, pa.eps, pf.eps, h,
                                     mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
-                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm)
+                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm, f8d=f8d)
         po = layers[-1].post_feedforward_layernorm
         res, x = torch.empty_like(h), torch.empty_like(h)
         Kn.add_rmsnorm2_fwd(h, m, po.weight, self.norm.weight, po.eps, self.norm.eps, res, x)
@@ -535,6 +548,17 @@ class Gemma2ForCausalLM(nn.Module):
     def enable_lora_decode(self, enabled: bool = True):
         """Gemma2Model.enable_lora_decode: the KV-cached forward with unmerged LoRA adapters (opt-in)."""
         self.model.enable_lora_decode(enabled)
+
+    def enable_fp8_decode(self, enabled: bool = True):
+        """Gemma2Model.enable_fp8_decode, and the decode head (head(decode=True)) on an e4m3 copy of lm_head."""
+        self.model.enable_fp8_decode(enabled)
+        self._svla_fp8_decode_head = Fn.FP8DecodeWeights() if enabled else None
+
+    def fp8_decode_holders(self):
+        """Every FP8DecodeWeights of the model (the layers', then the head's); [] with the switch off."""
+        hs = [getattr(l, "_svla_fp8_decode", None) for l in self.model.layers]
+        hs.append(getattr(self, "_svla_fp8_decode_head", None))
+        return [h for h in hs if h is not None]
 
     def set_decoder(self, decoder):
         self.model = decoder
@@ -579,8 +603,10 @@ class Gemma2ForCausalLM(nn.Module):
                              "attention_mask": attention_mask})
         return model_inputs
 
-    def head(self, hidden_states, target, stash):
-        """lm_head + softcap (reference :993-997) fused with the shifted CE; returns (logits2d, loss)."""
+    def head(self, hidden_states, target, stash, decode: bool = False):
+        """lm_head + softcap (reference :993-997) fused with the shifted CE; returns (logits2d, loss).  decode: the
+        rows are a KV-cached decode step's (cache position > 0) -- with enable_fp8_decode they run on the e4m3 copy of
+        lm_head (M <= 8 no-grad rows; other shapes keep the bf16 head); the prefill's head never does."""
         pwait = getattr(self, "_svla_param_wait", None)
         if pwait is not None:
             pwait("head")
@@ -590,6 +616,9 @@ class Gemma2ForCausalLM(nn.Module):
         ad = getattr(self.lm_head, "lora", None)  # add_lora("spatialvla-linear+emb+h"): the adapter on lm_head
         adapter = () if ad is None else (ad.scaling, ad.r, ad.A, ad.B)
         h2d = hidden_states.reshape(-1, hidden_states.shape[-1])
+        f8d = getattr(self, "_svla_fp8_decode_head", None) if decode and ad is None else None
+        if f8d is not None and self.lm_head.weight.stride(1) == 1 and Fn.lm_head_fp8_decode_ok(h2d):
+            return Fn.lm_head_fp8_decode(h2d, self.lm_head.weight, target, cap, stash, f8d)
         if ad is not None and Fn.lm_head_lora_decode_ok(h2d, ad.r):
             # a decode step's rows under the adapter: T, one pass over lm_head (svla_lora_head_gemv), finalize
             return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter)

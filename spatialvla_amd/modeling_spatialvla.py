@@ -568,7 +568,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 cnt = int(cnt[0])
             if cnt > 0:
                 stash["label_rows"] = order[:cnt]
-        logits2d, loss = self.language_model.head(h, target, stash)
+        logits2d, loss = self.language_model.head(h, target, stash, decode=past > 0)
         self.last_stash = stash
         logits = logits2d.view(B, Lq, -1) if logits2d is not None else None
         if num_logits_to_keep and logits is not None:
@@ -669,6 +669,64 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         for layer in self.language_model.model.layers:
             layer.set_fp8_projections(enabled)  # off: also turns enable_fp8_lora off
         self.clear_decode_cache()
+
+    @property
+    def fp8_decode(self) -> bool:
+        return bool(self.language_model.model.fp8_decode)
+
+    def enable_fp8_decode(self, enabled: bool = True):
+        """Weight-only MX fp8 decode (opt-in): the decode steps of predict_action, generate and
+        forward(past_key_values=...) -- cache position > 0, at most 8 new token rows -- stream OCP MX e4m3 copies of the
+        Gemma2 q|k|v, o, gate|up and down weights and of lm_head (svla_quant_mx_rows' values and exponents, dequantised
+        in registers by svla_gemv_mxfp8 / svla_head_gemv_mxfp8) instead of the bf16 weights: half the bytes per token.
+        Activations, the fp32 accumulation, norms, RoPE, attention, the KV cache and the softcap are unchanged, and the
+        prefill keeps the bf16 weights (bitwise the prefill of a model without the switch).  The copies (about 2.6 GiB
+        + 1/32 of that in exponents at 4B, beside the bf16 weights) are built by the first fp8 decode step and rebuilt
+        when a weight moved, changed in place or the optimizer stepped; shapes the kernels refuse (more than 8 rows, a
+        width that is no multiple of 128) keep the bf16 path.  Independent of enable_fp8_projections (the training
+        step's fp8 GEMMs); with both on the decode steps take this path.  Not combined with LoRA adapters: refused while
+        adapters are attached (merge_lora() first), and add_lora / load_lora are refused while it is on.  Toggling drops
+        the captured decode states."""
+        if enabled and (self.has_lora or self._emb_adapter is not None or self._head_adapter is not None):
+            raise RuntimeError("enable_fp8_decode: LoRA adapters are attached: call merge_lora() first (the e4m3 decode "
+                               "copies are made from the merged weights)")
+        self.language_model.enable_fp8_decode(enabled)
+        self.clear_decode_cache()
+
+    def _refuse_lora_under_fp8_decode(self, what: str):
+        if self.fp8_decode:
+            raise RuntimeError(f"{what}: weight-only fp8 decode is on (enable_fp8_decode): call "
+                               "enable_fp8_decode(False) first -- the e4m3 decode copies hold the base weights only")
+
+    def _fp8_decode_key(self):
+        """What the captured decode graphs bake in about the fp8 decode: None with the switch off, else the count of
+        this model's copy (re)builds after making every copy current -- the graphs hold raw pointers into the copies.
+        predict_action asks on every call, so the walk over the 4 x layers + 1 copies is skipped while a cheap stamp of
+        the quantised weights (WEIGHT_EPOCH, their summed tensor versions and addresses) is what it was at the last
+        walk; clear_decode_cache() forgets the stamp (a rebound parameter is a new tensor object)."""
+        if not self.fp8_decode:
+            return None
+        lm = self.language_model
+        memo = self.__dict__.get("_svla_fp8_decode_memo")
+        if memo is not None and memo[1] == self._fp8_decode_stamp(memo[0]):
+            return memo[2]
+        with torch.no_grad():
+            for layer in lm.model.layers:
+                f8d, at, mlp = layer._svla_fp8_decode, layer.self_attn, layer.mlp
+                f8d.get("qkv", [at.q_proj.weight, at.k_proj.weight, at.v_proj.weight])
+                f8d.get("o", [at.o_proj.weight])
+                f8d.get("gate_up", [mlp.gate_proj.weight, mlp.up_proj.weight])
+                f8d.get("down", [mlp.down_proj.weight])
+            lm._svla_fp8_decode_head.get("lm_head", [lm.lm_head.weight])
+        key = (True, sum(h.builds for h in lm.fp8_decode_holders()))
+        ws = [lin.weight for _, lin in self._lora_linears()] + [lm.lm_head.weight]
+        self.__dict__["_svla_fp8_decode_memo"] = (ws, self._fp8_decode_stamp(ws), key)
+        return key
+
+    def _fp8_decode_stamp(self, ws):
+        holders = self.language_model.fp8_decode_holders()
+        return (Fn.WEIGHT_EPOCH[0], sum(w._version for w in ws), sum(w.data_ptr() for w in ws),
+                sum(h.builds for h in holders))
 
     @property
     def fp8_lora(self) -> bool:
@@ -863,6 +921,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         --adpt_feature recipe, LoRA everywhere plus the spatial table trained in full (spatial_embed_tokens.weight
         keeps requires_grad=True; Fn.EmbedMergeFn's backward produces its gradient) and stored in the adapter file.
         Valid with any target set that does not itself adapt spatial_embed_tokens (both together: ValueError)."""
+        self._refuse_lora_under_fp8_decode("add_lora")
         if not isinstance(r, int) or r % 8 != 0 or not 8 <= r <= 64:
             raise ValueError(f"add_lora: r must be a multiple of 8 in [8, 64], got {r!r}")
         if isinstance(target_modules, str):
@@ -1030,6 +1089,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         import json
         import re
         from safetensors.torch import load_file
+        self._refuse_lora_under_fp8_decode("load_lora")
         with open(os.path.join(load_directory, "adapter_config.json")) as f:
             cfg = json.load(f)
         if cfg.get("peft_type", "LORA") != "LORA":
@@ -1131,6 +1191,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         The graphs hold raw pointers to the weights they were captured with, so anything that rebinds parameter
         storage (TrainEngine's flat buffers, load_state_dict with assign, .to()) must call this."""
         self.__dict__["_svla_decode_states"] = {}
+        self.__dict__.pop("_svla_fp8_decode_memo", None)
 
     @staticmethod
     def _prompt_positions(valid: torch.Tensor) -> torch.Tensor:
@@ -1156,7 +1217,9 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         # e4m3 weight copies, which the next eager forward after an optimizer step (WEIGHT_EPOCH) frees and rebuilds
         fp8 = any(getattr(l.mlp, "_svla_fp8", None) is not None for l in self.language_model.model.layers)
         # ... and to the LoRA adapters (rebound by TrainEngine / load_lora), with the path the switch selects
-        wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1, self._adapter_key())
+        # ... and, with the weight-only fp8 decode, to its e4m3 copies: the switch and the copies' identity
+        wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1, self._adapter_key(),
+                self._fp8_decode_key())
         if st is not None and st["wptr"] != wptr:  # weights were rebound since capture: the graphs are stale
             states.pop(key)
             st = None
@@ -1244,7 +1307,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         h, _ = self.language_model.model(self._merge_inputs(tok, None), st["cls"], pos, cache=cache)
         stash = {}
         tgt = torch.full((tok.shape[0],), -1, dtype=torch.int64, device=tok.device)
-        self.language_model.head(h[:, -1:].contiguous(), tgt, stash)
+        self.language_model.head(h[:, -1:].contiguous(), tgt, stash, decode=True)
         return stash["argmax"]
 
     def _greedy_bookkeep(self, st, p0, am):

@@ -103,6 +103,131 @@ def lora_main(args):
         "data": "synthetic OXE-shaped prompt, random-init weights and adapters"}), flush=True)
 
 
+def fp8_main(args):
+    """--fp8: ms per decode token of the bf16 decode and of the weight-only MX fp8 decode (enable_fp8_decode) in one
+    process, alternating rounds (one model each, warmed up and captured under its own setting, so the rounds only
+    replay), the bytes a token streams in each, the achieved GB/s against the 8 TB/s spec and the 6.3 TB/s measured copy
+    rate, the share of the greedy tokens on which the two agree, and a per-kernel table of the step: every projection
+    kernel of both paths timed over the 26 layers' own weights back to back (cold weights, as in the step)."""
+    from bench import build_model, make_batch
+    from spatialvla_amd import functional as Fn, kernels as K, presets
+    dev = torch.device("cuda:0")
+    cfgd = json.loads(json.dumps(presets.spatialvla_4b()))
+    b = make_batch(cfgd, args.batch, 4321, dev)
+    P = int((b["token_type_ids"][0] == 0).sum())
+    inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
+    n_long = args.new_tokens + args.long
+    models, toks = {}, {}
+    for name in ("bf16", "fp8"):
+        m = build_model(cfgd, dev).eval()
+        if name == "fp8":
+            m.enable_fp8_decode()
+        with torch.no_grad():
+            m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1)
+            toks[name] = m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1)
+        models[name] = m
+    rounds = []
+    with torch.no_grad():
+        for _ in range(args.rounds):
+            row = {}
+            for name, m in models.items():
+                t1, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1), args.reps)
+                tl, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1),
+                              max(3, args.reps // 2))
+                row[name] = {"ms_prefill_plus_first": round(t1, 2), "ms_per_decode_token": round((tl - t1) / (n_long - 1), 4)}
+            rounds.append(row)
+    per = {n: [r[n]["ms_per_decode_token"] for r in rounds] for n in models}
+    lm = models["bf16"].language_model
+    norms = sum(p.numel() * p.element_size() for n, p in lm.model.named_parameters() if "norm" in n)
+    nbytes = {"bf16": sum(p.numel() * p.element_size() for p in lm.model.layers.parameters())
+              + lm.lm_head.weight.numel() * lm.lm_head.weight.element_size()
+              + lm.model.norm.weight.numel() * lm.model.norm.weight.element_size(),
+              "fp8": sum(h.nbytes() for h in models["fp8"].language_model.fp8_decode_holders()) + norms}
+    best = {n: min(v) for n, v in per.items()}
+    gbs = {n: nbytes[n] / (best[n] * 1e-3) / 1e9 for n in models}
+
+    # per-kernel table: one launch per layer over that layer's own weights, the median of `reps` such sweeps; every row
+    # calls the kernel bindings directly on preallocated outputs, so the rows carry the same host cost per launch
+    tc = lm.config
+    H, I = tc.hidden_size, tc.intermediate_size
+    qd = tc.num_attention_heads * tc.head_dim
+    kd = tc.num_key_value_heads * tc.head_dim
+    M = args.batch
+    g = torch.Generator(device="cpu").manual_seed(3)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).to(dev)  # noqa: E731
+    res, y, attn, hout = rnd(M, H), rnd(M, H), rnd(M, qd), torch.empty(M, H, dtype=torch.bfloat16, device=dev)
+    qkv, out = (torch.empty(M, n, dtype=torch.bfloat16, device=dev) for n in (qd + 2 * kd, H))
+    hact, gbuf, ubuf = (torch.empty(M, I, dtype=torch.bfloat16, device=dev) for _ in range(3))
+    tgt = torch.full((M,), -1, dtype=torch.int64, device=dev)
+
+    def sweep(fn, layers):
+        def run():
+            for l in layers:
+                fn(l)
+        with torch.no_grad():
+            run()
+            t, _ = timed(run, args.reps)
+        return t * 1e3 / len(layers)
+
+    table = {}
+    for name, m in models.items():
+        layers = list(m.language_model.model.layers)
+        f8 = name == "fp8"
+
+        def pre(l):
+            pa, pf = l.post_attention_layernorm, l.pre_feedforward_layernorm
+            return (res, y, pa.weight, pf.weight, pa.eps, pf.eps, hout)
+
+        def k_qkv(l):
+            ws = [l.self_attn.q_proj.weight, l.self_attn.k_proj.weight, l.self_attn.v_proj.weight]
+            if f8:
+                K.gemv_mxfp8(None, *l._svla_fp8_decode.get("qkv", ws), qkv, norm=pre(l))
+            else:
+                K.gemv_rmsnorm2(*pre(l), ws, qkv)
+
+        def k_o(l):
+            if f8:
+                K.gemv_mxfp8(attn, *l._svla_fp8_decode.get("o", [l.self_attn.o_proj.weight]), out)
+            else:
+                K.linear_fwd(attn, [l.self_attn.o_proj.weight], out)
+
+        def k_mlp(l):
+            wg, wu, wd = l.mlp.gate_proj.weight, l.mlp.up_proj.weight, l.mlp.down_proj.weight
+            if f8:  # the two launches of Fn.gemma_mlp_decode(f8d=...)
+                K.gemv_mxfp8(None, *l._svla_fp8_decode.get("gate_up", [wg, wu]), hact, geglu_out=(gbuf, ubuf),
+                             norm=pre(l))
+                K.gemv_mxfp8(hact, *l._svla_fp8_decode.get("down", [wd]), out)
+            elif Fn.persist_ok(y, wg, wu, wd):  # the one persistent launch of Fn.gemma_mlp_decode
+                K.decode_mlp(*pre(l), wg, wu, wd, hact, out)
+            else:
+                K.gemv_rmsnorm2(*pre(l), [wg, wu], hact, geglu_out=(gbuf, ubuf))
+                K.linear_fwd(hact, [wd], out)
+
+        hrow = rnd(M, 1, H)
+        table[name] = {"qkv_with_norm_pair_us": round(sweep(k_qkv, layers), 2), "o_us": round(sweep(k_o, layers), 2),
+                       "mlp_with_norm_pair_us": round(sweep(k_mlp, layers), 2),
+                       "head_us": round(sweep(lambda _l: m.language_model.head(hrow, tgt, {}, decode=True), [None]), 2)}
+        table[name]["sum_per_step_us"] = round(sum(table[name][k] * (1 if k == "head_us" else len(layers))
+                                                   for k in list(table[name])), 1)
+    agree = float((toks["bf16"] == toks["fp8"]).float().mean())
+    print(json.dumps({
+        "metric": "SpatialVLA-4B greedy decode latency, bf16 against weight-only MX fp8 decode", "unit": "ms",
+        "batch": args.batch, "prompt_tokens": P, "decode_tokens_timed": n_long - 1, "rounds": rounds,
+        "ms_per_decode_token_min_max": {n: [min(v), max(v)] for n, v in per.items()},
+        "bytes_per_token": nbytes,
+        "achieved_GBps": {n: round(v, 1) for n, v in gbs.items()},
+        "frac_of_8TBps_spec": {n: round(v / 8000.0, 4) for n, v in gbs.items()},
+        "frac_of_6p3TBps_copy": {n: round(v / 6300.0, 4) for n, v in gbs.items()},
+        "greedy_tokens": n_long, "tokens_agree_share": round(agree, 4),
+        "kernels": table,
+        "kernels_note": "wall us per eager launch (host launch cost included: an upper bound of the kernel time, not a "
+                        "kernel trace), one launch per layer over that layer's weights, kernel bindings on preallocated "
+                        "outputs (head: the model's head() on lm_head, warm, with its allocations); the bf16 mlp is the "
+                        "persistent svla_decode_mlp, the fp8 mlp the norm-prologue gate|up GEMV + the down GEMV",
+        "decode_graphs": bool(models["bf16"].decode_graphs),
+        "data": "synthetic OXE-shaped prompt, random-init weights"}), flush=True)
+
+
 VARIANTS = "merged,adapters_kernels,adapters_composed"
 
 
@@ -121,10 +246,15 @@ def main():
     ap.add_argument("--variants", default=VARIANTS,
                     help="--lora: which of merged, adapters_kernels, adapters_composed (with an +emb set also "
                          "adapters_kernels_ends_composed, added by default) to run (a kernel trace takes one)")
-    ap.add_argument("--rounds", type=int, default=3, help="--lora: alternating rounds")
+    ap.add_argument("--rounds", type=int, default=3, help="--lora / --fp8: alternating rounds")
+    ap.add_argument("--fp8", action="store_true",
+                    help="bf16 against the weight-only MX fp8 decode (enable_fp8_decode), alternating rounds, bytes per "
+                         "token, token agreement and a per-kernel table")
     args = ap.parse_args()
     if args.lora:
         return lora_main(args)
+    if args.fp8:
+        return fp8_main(args)
     from bench import build_model, make_batch
     from spatialvla_amd import presets
     dev = torch.device("cuda:0")
