@@ -395,6 +395,32 @@ int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
 int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q, int64_t ldq,
                          const void* xs, int64_t lds, float cap, void* logits, int64_t ld, float* row_stats,
                          void* stream);
+/* svla_lora_gemv_mxfp8: svla_lora_gemv over the e4m3 copy of a frozen base weight -- the decode step of a model whose
+ * adapters are still unmerged (peft's base(x) + lora_B(lora_A(x)) * s, train/spatialvla_finetune.py:262-300) streams
+ * half the base bytes and adds the rank-r term in bf16 inside the same pass:
+ *   y[m,n] = bf16( bf16( sum_b 2^X(n,b) sum_{k in b} x[m,k] q[n,k] ) + bf16( scaling sum_j T[m, sR+j] B_s[n - start_s, j] ) )
+ * The base sum is svla_gemv_mxfp8's, bit for bit for the same K (K > 4096 STORE: its split-K form), the adapter term
+ * and the two roundings are svla_lora_gemv's: the output equals bf16(y0 + yad) with y0 = svla_gemv_mxfp8 and yad =
+ * svla_lora_gemv on an all-zero W, and with B = 0 it is y0.  Epilogues: SVLA_EPI_STORE (up to three row segments,
+ * q|k|v) and SVLA_EPI_GEGLU (gate|up: the adapted g, u to epi->out1 / out2, c [M][I] = SVLA_EPI_GEGLU's element
+ * formula on them); there is no norm-prologue form (svla_lora_gemv_down's norm form stores x).  The restrictions are
+ * the union of the parents': M <= 8, N >= 16, K % 128 == 0, W->ldq % 16 == 0, exponents in svla_mx_scales_rowmajor's
+ * layout, bsegs by svla_lora_up's SLICED rules (starts multiples of 16 from 0 to N, r a multiple of 8 in 8..64) with
+ * one B segment per weight segment at the same starts, T from svla_lora_gemv_down (16-B aligned, ldt >= (nseg-1) R +
+ * r).  A shape error both forms share is reported under svla_gemv_mxfp8's name. */
+int svla_lora_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_mxfp8_rows* W,
+                         const void* t, int64_t ldt, const svla_lora_segs* bsegs, float scaling, void* c, int64_t ldc,
+                         const svla_epilogue* epi, void* stream);
+/* svla_lora_head_gemv_mxfp8: the decode head over the e4m3 lm_head with an unmerged lm_head adapter (lora_target
+ * "linear+emb+h", train/spatialvla_finetune.py:279-286): y as above with one segment (T [M][ldt], B [N][ldb]), then
+ * the logits and row_stats by the finishing stage svla_head_gemv_mxfp8 and svla_lora_head_gemv share -- bitwise
+ * svla_softcap_ce_rows applied to svla_lora_gemv_mxfp8's output, so svla_ce_finalize follows unchanged, and with
+ * B = 0 the result is svla_head_gemv_mxfp8's.  M <= 8, any N >= 1, K % 128 == 0, K <= 4096; r a multiple of 8 in
+ * 8..64; ldb, ldt multiples of 8 >= r; x, q, t, B, logits 16-B aligned. */
+int svla_lora_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q, int64_t ldq,
+                              const void* xs, int64_t lds, const void* t, int64_t ldt, const void* B, int64_t ldb,
+                              int32_t r, float scaling, float cap, void* logits, int64_t ld, float* row_stats,
+                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via

@@ -137,6 +137,10 @@ SIGNATURES = {
                                 c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
     "svla_head_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_i64,
                                      c_vp, c_vp]),
+    "svla_lora_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(MxFp8Rows), c_vp, c_i64,
+                                     ctypes.POINTER(LoraSegs), c_f32, c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
+    "svla_lora_head_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                          c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

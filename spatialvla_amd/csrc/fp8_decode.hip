@@ -1,5 +1,6 @@
 // Weight-only OCP MX e4m3 GEMVs of the KV-cached decode step for gfx950 (MI355X): svla_mx_scales_rowmajor,
-// svla_gemv_mxfp8 and svla_head_gemv_mxfp8 (include/svla.h).
+// svla_gemv_mxfp8 and svla_head_gemv_mxfp8, and their forms under unmerged LoRA adapters, svla_lora_gemv_mxfp8 and
+// svla_lora_head_gemv_mxfp8 (include/svla.h).
 //
 // A decode step streams every Gemma2 projection weight and lm_head once from HBM; with the weights kept as the e4m3
 // values of svla_quant_mx_rows (one E8M0 exponent per 32 consecutive k) a token moves half the bytes.  Activations stay
@@ -19,9 +20,15 @@
 //                      svla_softcap_ce_rows), each wave walks its rows with mxg_kernel's per-row dot product (the next
 //                      row in flight while this one is summed) and leaves the raw bf16 logit in LDS; 16 lanes per
 //                      token row then run svla_softcap_ce_rows' per-element unit and group combine.
+// Under unmerged adapters (the AD instances of mxg_kernel, mxg_splitk_kernel and mxh_kernel) the frozen base weight is
+// the e4m3 copy and the rank-r term is added in bf16 inside the same pass, as lora_decode.hip does over bf16 weights:
+// lane j < r holds B[n, j] and T[m, j] (lora_adapter.h), one product per lane and a wave butterfly, then
+// y = bf16(bf16(base) + bf16(s l)).  The base sum is the AD = false instance's, bit for bit; the adapter operands are
+// loaded ahead of the weight stream, and the M = 1 instances keep the occupancy of their parents within one wave.
 // fp32 accumulation in a fixed order (fmaf only, so the contraction mode cannot change it), 16-B non-temporal weight
 // reads, no atomics, no block waits for another block, no allocation and no host synchronisation (graph-capturable).
 #include "softcap_tab.h"
+#include "lora_adapter.h"
 
 namespace {
 
@@ -53,6 +60,19 @@ struct MxOut {
   bf16_t* g;
   bf16_t* u;
   int64_t ldc, ldg, ldu;
+};
+struct MxAd {  // the unmerged adapters of svla_lora_gemv_mxfp8: T [M][ldt], the B segments, the scaling
+  const bf16_t* T;
+  int64_t ldt;
+  Segs S;
+  float sc;
+};
+struct MxHeadAd {  // the lm_head adapter of svla_lora_head_gemv_mxfp8
+  const bf16_t* T;
+  const bf16_t* B;
+  int64_t ldt, ldb;
+  int r;
+  float sc;
 };
 
 // e4m3 row n and its exponent row of a weight of up to three row segments (q|k|v)
@@ -141,13 +161,27 @@ __device__ __forceinline__ void mx_store(const MxOut& O, int m, int64_t n, float
 // ------------------------------------------------------------------------------------------------ mxg_kernel
 // KCH > 0: K <= 1024 KCH, every chunk of the wave's two rows loaded before the first FMA; KCH == 0: a runtime loop
 // (the same per-lane order).  rows: output rows (GEGLU: I, the wave's two weight rows are gate row n and up row n).
-template <int KCH, bool GEGLU, int MR>
+// AD (svla_lora_gemv_mxfp8): each of the wave's two rows also carries its adapter operands (lora_adapter.h), loaded
+// ahead of the weight stream, and its sum goes through ad_finish; the base sum is the AD = false instance's.
+template <int KCH, bool GEGLU, int MR, bool AD>
 __global__ __launch_bounds__(256) void mxg_kernel(int M, int64_t rows, int64_t K, const bf16_t* __restrict__ x,
-                                                  int64_t ldx, MxRows W, MxOut O) {
+                                                  int64_t ldx, MxRows W, MxOut O, MxAd A) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t r0 = GEGLU ? wave : wave * 2;
   if (r0 >= rows) return;
+  AdRow<MR> ad[2];
+  if constexpr (AD) {
+    if constexpr (GEGLU) {
+      ad_load(ad[0], A.S, 0, r0, A.T, A.ldt, M, lane);
+      ad_load(ad[1], A.S, 1, r0, A.T, A.ldt, M, lane);
+    } else {
+      const int64_t r1 = r0 + 1 < rows ? r0 + 1 : rows - 1;
+      const int s0 = seg_of(A.S, r0), s1 = seg_of(A.S, r1);
+      ad_load(ad[0], A.S, s0, r0 - seg_st(A.S, s0), A.T, A.ldt, M, lane);
+      ad_load(ad[1], A.S, s1, r1 - seg_st(A.S, s1), A.T, A.ldt, M, lane);
+    }
+  }
   const uint8_t *qp[2], *sp[2];
   if constexpr (GEGLU) {
     qp[0] = W.q0 + r0 * W.ldq;
@@ -200,7 +234,11 @@ __global__ __launch_bounds__(256) void mxg_kernel(int M, int64_t rows, int64_t K
 #pragma unroll
   for (int m = 0; m < MR; ++m) {
     if (m < M) {
-      const float v0 = wave_sum(acc[0][m]), v1 = wave_sum(acc[1][m]);
+      float v0 = wave_sum(acc[0][m]), v1 = wave_sum(acc[1][m]);
+      if constexpr (AD) {
+        v0 = ad_finish(ad[0], m, v0, A.sc);
+        v1 = ad_finish(ad[1], m, v1, A.sc);
+      }
       if (lane == 0) {
         if constexpr (GEGLU) {
           mx_store<true>(O, m, r0, v0, v1);
@@ -357,13 +395,22 @@ __global__ __launch_bounds__(256) void mxg_norm2_kernel(int M, int64_t rows, int
 
 // ------------------------------------------------------------------------------------------------ mxg_splitk_kernel
 // One block per output row: thread t owns k = 16 t + 4096 i (K <= 12288: all three chunks in flight at once), the four
-// waves' partial sums are added in wave order.
-template <int MR>
+// waves' partial sums are added in wave order.  AD: wave 0 also carries the row's adapter term (lora_decode.hip's
+// lg_split_kernel), left in part[4].
+template <int MR, bool AD>
 __global__ __launch_bounds__(256) void mxg_splitk_kernel(int M, int64_t rows, int64_t K, const bf16_t* __restrict__ x,
-                                                         int64_t ldx, MxRows W, bf16_t* __restrict__ c, int64_t ldc) {
-  __shared__ float part[4][MXG_MAXM];
+                                                         int64_t ldx, MxRows W, bf16_t* __restrict__ c, int64_t ldc,
+                                                         MxAd A) {
+  __shared__ float part[AD ? 5 : 4][MXG_MAXM];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n = blockIdx.x;
+  AdRow<MR> ad;
+  if constexpr (AD) {
+    if (w == 0) {  // wave-uniform
+      const int s = seg_of(A.S, n);
+      ad_load(ad, A.S, s, n - seg_st(A.S, s), A.T, A.ldt, M, lane);
+    }
+  }
   const uint8_t *qp, *sp;
   mx_row(W, n, qp, sp);
   float acc[1][MR];
@@ -401,12 +448,20 @@ __global__ __launch_bounds__(256) void mxg_splitk_kernel(int M, int64_t rows, in
     if (m < M) {
       const float v = wave_sum(acc[0][m]);
       if (lane == 0) part[w][m] = v;
+      if constexpr (AD) {
+        if (w == 0) {  // wave-uniform
+          const float l = wave_sum(ad.b * ad.t[m]);
+          if (lane == 0) part[4][m] = l;
+        }
+      }
     }
   }
   __syncthreads();
   if (threadIdx.x < M) {
     const int m = threadIdx.x;
-    c[m * ldc + n] = f2bf(((part[0][m] + part[1][m]) + part[2][m]) + part[3][m]);
+    const float base = ((part[0][m] + part[1][m]) + part[2][m]) + part[3][m];
+    if constexpr (AD) c[m * ldc + n] = f2bf(round_bf(round_bf(base) + round_bf(A.sc * part[4][m])));  // ad_finish
+    else c[m * ldc + n] = f2bf(base);
   }
 }
 
@@ -421,11 +476,14 @@ __device__ __forceinline__ float mxh_dppf(float x) {
 }
 constexpr int MXH_X1 = 0xb1, MXH_X2 = 0x4e, MXH_HALF_MIRROR = 0x141, MXH_MIRROR = 0x140;  // softcap.hip's butterfly
 
-template <int KCH, int MR>
+// AD (svla_lora_head_gemv_mxfp8): lane j < r also holds T[m, j] and, with each weight row, B[n, j]; the raw logit is
+// lora_decode.hip lh_kernel's y = bf16(bf16(base) + bf16(s T B)).
+template <int KCH, int MR, bool AD>
 __global__ __launch_bounds__(256) void mxh_kernel(int M, int64_t N, int64_t K, const bf16_t* __restrict__ x, int64_t ldx,
                                                   const uint8_t* __restrict__ Q, int64_t ldq,
                                                   const uint8_t* __restrict__ S, int64_t lds, float cap,
-                                                  bf16_t* __restrict__ lg, int64_t ld, float* __restrict__ row_stats) {
+                                                  bf16_t* __restrict__ lg, int64_t ld, float* __restrict__ row_stats,
+                                                  MxHeadAd A) {
   __shared__ __attribute__((aligned(16))) unsigned short tab[TANH_TAB_BYTES / 2 + 8];
   __shared__ __attribute__((aligned(16))) bf16_t ys[MXG_MAXM][MXH_COLS];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -433,9 +491,16 @@ __global__ __launch_bounds__(256) void mxh_kernel(int M, int64_t N, int64_t K, c
     reinterpret_cast<u32x4*>(tab)[tid] = reinterpret_cast<const u32x4*>(svla_tanh_bf16_tab)[tid];
   const int64_t n0 = (int64_t)blockIdx.x * MXH_COLS;
   const int nrow = (int)(N - n0 < MXH_COLS ? N - n0 : MXH_COLS);
-  auto load_row = [&](int64_t n, u32x4 (&w)[KCH][1], uint32_t (&sb)[KCH][1]) {
+  const bool on = AD && lane < A.r;
+  float tv[MR];
+  if constexpr (AD) {
+#pragma unroll
+    for (int m = 0; m < MR; ++m) tv[m] = (on && m < M) ? bf2f(A.T[m * A.ldt + lane]) : 0.f;
+  }
+  auto load_row = [&](int64_t n, u32x4 (&w)[KCH][1], uint32_t (&sb)[KCH][1], float& b) {
     const uint8_t* qr = Q + n * ldq;
     const uint8_t* sr = S + n * lds;
+    if constexpr (AD) b = on ? bf2f(A.B[n * A.ldb + lane]) : 0.f;
 #pragma unroll
     for (int i = 0; i < KCH; ++i) {
       const int64_t k = (int64_t)lane * 16 + i * 1024;
@@ -454,9 +519,10 @@ __global__ __launch_bounds__(256) void mxh_kernel(int M, int64_t N, int64_t K, c
     wc[i][0] = wn[i][0] = u32x4{0u, 0u, 0u, 0u};
     sc[i][0] = sn[i][0] = 0u;
   }
-  if (wv < nrow) load_row(n0 + wv, wc, sc);
+  float bc = 0.f, bn = 0.f;
+  if (wv < nrow) load_row(n0 + wv, wc, sc, bc);
   for (int i = wv; i < nrow; i += 4) {  // wave-uniform
-    if (i + 4 < nrow) load_row(n0 + i + 4, wn, sn);
+    if (i + 4 < nrow) load_row(n0 + i + 4, wn, sn, bn);
     float acc[1][MR];
 #pragma unroll
     for (int m = 0; m < MR; ++m) acc[0][m] = 0.f;
@@ -468,7 +534,8 @@ __global__ __launch_bounds__(256) void mxh_kernel(int M, int64_t N, int64_t K, c
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
       if (m < M) {
-        const float y = wave_sum(acc[0][m]);
+        float y = wave_sum(acc[0][m]);
+        if constexpr (AD) y = round_bf(round_bf(y) + round_bf(A.sc * wave_sum(bc * tv[m])));  // ad_finish
         if (lane == 0) ys[m][i] = f2bf(y);
       }
     }
@@ -477,6 +544,7 @@ __global__ __launch_bounds__(256) void mxh_kernel(int M, int64_t N, int64_t K, c
       wc[c][0] = wn[c][0];
       sc[c][0] = sn[c][0];
     }
+    bc = bn;
   }
   __syncthreads();
   if (tid >= 16 * MXG_MAXM) return;  // whole waves leave
@@ -562,8 +630,12 @@ extern "C" int svla_mx_scales_rowmajor(int64_t rows, int64_t K, const void* scal
   return svla::check_launch("mx_scales_rowmajor");
 }
 
-extern "C" int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_lora_norm2* norm,
-                               const svla_mxfp8_rows* W, void* c, int64_t ldc, const svla_epilogue* epi, void* stream) {
+namespace {
+
+// svla_gemv_mxfp8 (ad == nullptr) and svla_lora_gemv_mxfp8 (ad: T, ldt, the scaling and the validated B segments)
+template <bool AD>
+int mx_gemv(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_lora_norm2* norm,
+            const svla_mxfp8_rows* W, void* c, int64_t ldc, const svla_epilogue* epi, const MxAd& A, void* stream) {
   SVLA_CHECK_ARG(M >= 1 && M <= MXG_MAXM && N >= 1 && K >= 128 && K % 128 == 0,
                  "gemv_mxfp8: M in [1, %d], N >= 1, K a positive multiple of 128 (M %lld, N %lld, K %lld)", MXG_MAXM,
                  (long long)M, (long long)N, (long long)K);
@@ -609,7 +681,7 @@ extern "C" int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, i
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
   const int kch = (int)((K + 1023) / 1024);
   hipStream_t s = (hipStream_t)stream;
-  if (norm) {
+  if (!AD && norm) {
     SVLA_CHECK_ARG(K <= MXG_NORM_MAX_K, "gemv_mxfp8: the norm prologue holds rows of K <= %d, got %lld", MXG_NORM_MAX_K,
                    (long long)K);
     SVLA_CHECK_ARG(norm->res && norm->y && norm->w1 && norm->w2 && norm->h_out && al16(norm->res) && al16(norm->y) &&
@@ -642,15 +714,15 @@ extern "C" int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, i
                  "multiple of 8 >= K");
   if (!geglu && K > 4096) {  // long K (the down projection): the block-per-row split-K form
     if (M == 1)
-      hipLaunchKernelGGL((mxg_splitk_kernel<1>), dim3((unsigned)rows), block, 0, s, (int)M, rows, K, (const bf16_t*)x,
-                         ldx, R, (bf16_t*)c, ldc);
+      hipLaunchKernelGGL((mxg_splitk_kernel<1, AD>), dim3((unsigned)rows), block, 0, s, (int)M, rows, K,
+                         (const bf16_t*)x, ldx, R, (bf16_t*)c, ldc, A);
     else
-      hipLaunchKernelGGL((mxg_splitk_kernel<MXG_MAXM>), dim3((unsigned)rows), block, 0, s, (int)M, rows, K,
-                         (const bf16_t*)x, ldx, R, (bf16_t*)c, ldc);
-    return svla::check_launch("gemv_mxfp8 (split-K)");
+      hipLaunchKernelGGL((mxg_splitk_kernel<MXG_MAXM, AD>), dim3((unsigned)rows), block, 0, s, (int)M, rows, K,
+                         (const bf16_t*)x, ldx, R, (bf16_t*)c, ldc, A);
+    return svla::check_launch(AD ? "lora_gemv_mxfp8 (split-K)" : "gemv_mxfp8 (split-K)");
   }
 #define SVLA_MXG1(KC, GG, MR_) \
-  hipLaunchKernelGGL((mxg_kernel<KC, GG, MR_>), grid, block, 0, s, (int)M, rows, K, (const bf16_t*)x, ldx, R, O)
+  hipLaunchKernelGGL((mxg_kernel<KC, GG, MR_, AD>), grid, block, 0, s, (int)M, rows, K, (const bf16_t*)x, ldx, R, O, A)
 #define SVLA_MXG(KC)                              \
   do {                                            \
     if (geglu) {                                  \
@@ -668,12 +740,38 @@ extern "C" int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, i
   else SVLA_MXG(0);
 #undef SVLA_MXG
 #undef SVLA_MXG1
-  return svla::check_launch("gemv_mxfp8");
+  return svla::check_launch(AD ? "lora_gemv_mxfp8" : "gemv_mxfp8");
 }
 
-extern "C" int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q,
-                                    int64_t ldq, const void* xs, int64_t lds, float cap, void* logits, int64_t ld,
-                                    float* row_stats, void* stream) {
+}  // namespace
+
+extern "C" int svla_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_lora_norm2* norm,
+                               const svla_mxfp8_rows* W, void* c, int64_t ldc, const svla_epilogue* epi, void* stream) {
+  return mx_gemv<false>(M, N, K, x, ldx, norm, W, c, ldc, epi, MxAd{}, stream);
+}
+
+extern "C" int svla_lora_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                    const svla_mxfp8_rows* W, const void* t, int64_t ldt, const svla_lora_segs* bsegs,
+                                    float scaling, void* c, int64_t ldc, const svla_epilogue* epi, void* stream) {
+  SVLA_CHECK_ARG(N >= 16, "lora_gemv_mxfp8: N >= 16, got %lld", (long long)N);
+  SVLA_CHECK_ARG(t && al16(t), "lora_gemv_mxfp8: t NULL or not 16-B aligned");
+  MxAd A = {(const bf16_t*)t, ldt, {}, scaling};
+  const int rc = make_segs("lora_gemv_mxfp8", bsegs, A.S, true, N);
+  if (rc != SVLA_OK) return rc;
+  SVLA_CHECK_ARG(A.S.ld >= A.S.r, "lora_gemv_mxfp8: the B matrices' ld is below r");
+  SVLA_CHECK_ARG(ldt >= (int64_t)(A.S.nseg - 1) * A.S.R + A.S.r,
+                 "lora_gemv_mxfp8: ldt must cover (nseg - 1) * R + r columns, got %lld", (long long)ldt);
+  SVLA_CHECK_ARG(W && W->nseg == A.S.nseg, "lora_gemv_mxfp8: one B segment per weight segment");
+  for (int i = 0; i <= A.S.nseg; ++i)
+    SVLA_CHECK_ARG(W->start[i] == A.S.st[i], "lora_gemv_mxfp8: the weight and the B segments must start at the same rows");
+  return mx_gemv<true>(M, N, K, x, ldx, nullptr, W, c, ldc, epi, A, stream);
+}
+
+namespace {
+
+template <bool AD>
+int mx_head(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q, int64_t ldq, const void* xs,
+            int64_t lds, float cap, void* logits, int64_t ld, float* row_stats, const MxHeadAd& A, void* stream) {
   SVLA_CHECK_ARG(M >= 1 && M <= MXG_MAXM && N >= 1 && N < (1ll << 31) && K >= 128 && K % 128 == 0 && K <= MXH_MAX_K,
                  "head_gemv_mxfp8: M in [1, %d], N >= 1, K a multiple of 128 in [128, %d] (M %lld, N %lld, K %lld)",
                  MXG_MAXM, MXH_MAX_K, (long long)M, (long long)N, (long long)K);
@@ -685,8 +783,8 @@ extern "C" int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void*
   const int kch = (int)((K + 1023) / 1024);
   const dim3 grid((unsigned)((N + MXH_COLS - 1) / MXH_COLS)), block(256);
 #define SVLA_MXH1(KC, MR_)                                                                                           \
-  hipLaunchKernelGGL((mxh_kernel<KC, MR_>), grid, block, 0, (hipStream_t)stream, (int)M, N, K, (const bf16_t*)x, ldx, \
-                     (const uint8_t*)q, ldq, (const uint8_t*)xs, lds, cap, (bf16_t*)logits, ld, row_stats)
+  hipLaunchKernelGGL((mxh_kernel<KC, MR_, AD>), grid, block, 0, (hipStream_t)stream, (int)M, N, K, (const bf16_t*)x, \
+                     ldx, (const uint8_t*)q, ldq, (const uint8_t*)xs, lds, cap, (bf16_t*)logits, ld, row_stats, A)
 #define SVLA_MXH(KC)                  \
   do {                                \
     if (M == 1) SVLA_MXH1(KC, 1);     \
@@ -697,5 +795,26 @@ extern "C" int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void*
   else SVLA_MXH(4);
 #undef SVLA_MXH
 #undef SVLA_MXH1
-  return svla::check_launch("head_gemv_mxfp8");
+  return svla::check_launch(AD ? "lora_head_gemv_mxfp8" : "head_gemv_mxfp8");
+}
+
+}  // namespace
+
+extern "C" int svla_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q,
+                                    int64_t ldq, const void* xs, int64_t lds, float cap, void* logits, int64_t ld,
+                                    float* row_stats, void* stream) {
+  return mx_head<false>(M, N, K, x, ldx, q, ldq, xs, lds, cap, logits, ld, row_stats, MxHeadAd{}, stream);
+}
+
+extern "C" int svla_lora_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const void* q,
+                                         int64_t ldq, const void* xs, int64_t lds, const void* t, int64_t ldt,
+                                         const void* B, int64_t ldb, int32_t r, float scaling, float cap, void* logits,
+                                         int64_t ld, float* row_stats, void* stream) {
+  SVLA_CHECK_ARG(t && B && al16(t) && al16(B), "lora_head_gemv_mxfp8: t / B NULL or not 16-B aligned");
+  SVLA_CHECK_ARG(r >= 8 && r <= MAX_R && r % 8 == 0,
+                 "lora_head_gemv_mxfp8: rank must be a multiple of 8 in [8, 64], got %d", (int)r);
+  SVLA_CHECK_ARG(ldb % 8 == 0 && ldb >= r && ldt % 8 == 0 && ldt >= r,
+                 "lora_head_gemv_mxfp8: ldb, ldt multiples of 8 >= r");
+  const MxHeadAd A = {(const bf16_t*)t, (const bf16_t*)B, ldt, ldb, (int)r, scaling};
+  return mx_head<true>(M, N, K, x, ldx, q, ldq, xs, lds, cap, logits, ld, row_stats, A, stream);
 }

@@ -19,21 +19,14 @@
 // fp32 accumulation in a fixed order, 16-B non-temporal weight reads issued before the first FMA, no atomics, no
 // block waits for another block, no allocation and no host synchronisation (graph-capturable).
 #include "softcap_tab.h"
+#include "lora_adapter.h"
 
 namespace {
 
 constexpr int LG_MAXM = 8;
-constexpr int MAX_SEG = 3;
-constexpr int MAX_R = 64;
 constexpr int GN_MAXC = 2;     // norm chunks per thread (256 threads x 8 elements x 2 >= 2560)
 constexpr int NORM_MAX_K = 2560;
 
-struct Segs {
-  const bf16_t* p[MAX_SEG];
-  int64_t st[MAX_SEG + 1];
-  int64_t ld;
-  int nseg, r, R;
-};
 struct Norm2 {  // svla_lora_norm2 with typed pointers
   const bf16_t* res;
   const bf16_t* y;
@@ -43,14 +36,6 @@ struct Norm2 {  // svla_lora_norm2 with typed pointers
   int64_t ld;
   float eps1, eps2;
 };
-
-__device__ __forceinline__ const bf16_t* seg_p(const Segs& S, int s) {
-  return s == 0 ? S.p[0] : (s == 1 ? S.p[1] : S.p[2]);
-}
-__device__ __forceinline__ int seg_of(const Segs& S, int64_t n) {
-  return (int)(S.nseg > 1 && n >= S.st[1]) + (int)(S.nseg > 2 && n >= S.st[2]);
-}
-__device__ __forceinline__ int64_t seg_st(const Segs& S, int s) { return s == 0 ? 0 : (s == 1 ? S.st[1] : S.st[2]); }
 
 // weight row n of a W operand with up to 4 outer segments (gemm.hip gemv_row)
 __device__ __forceinline__ const bf16_t* w_row(const svla_operand& W, int64_t n) {
@@ -273,27 +258,7 @@ __global__ __launch_bounds__(256) void lgd_split_kernel(int M, int64_t K, const 
 }
 
 // ------------------------------------------------------------------------------------------------ lora_gemv
-// The adapter operands of one output row: lane j < r holds B_s[row, j] and T[m, s R + j] (one value per lane: r <= 64).
-template <int MR>
-struct AdRow {
-  float b;
-  float t[MR];
-};
-template <int MR>
-__device__ __forceinline__ void ad_load(AdRow<MR>& a, const Segs& S, int s, int64_t row, const bf16_t* __restrict__ T,
-                                        int64_t ldt, int M, int lane) {
-  const bool on = lane < S.r;
-  a.b = on ? bf2f(seg_p(S, s)[row * S.ld + lane]) : 0.f;
-#pragma unroll
-  for (int m = 0; m < MR; ++m) a.t[m] = (on && m < M) ? bf2f(T[m * ldt + s * S.R + lane]) : 0.f;
-}
-// bf16(bf16(base) + bf16(s * sum_j T B)): svla_gemm_bf16's plain store followed by svla_lora_up
-template <int MR>
-__device__ __forceinline__ float ad_finish(const AdRow<MR>& a, int m, float base, float sc) {
-  const float l = wave_sum(a.b * a.t[m]);
-  return round_bf(round_bf(base) + round_bf(sc * l));
-}
-
+// The adapter operands of one output row (AdRow, ad_load, ad_finish) are lora_adapter.h's.
 struct LgOut {
   bf16_t* c;
   bf16_t* g;
@@ -614,37 +579,6 @@ __global__ __launch_bounds__(256) void lh_kernel(int M, int64_t N, int64_t K, co
     rs[1] = se;
     rs[2] = __int_as_float(am);
   }
-}
-
-// ------------------------------------------------------------------------------------------------ host side
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int make_segs(const char* what, const svla_lora_segs* in, Segs& S, bool need_starts, int64_t extent) {
-  SVLA_CHECK_ARG(in != nullptr, "%s: segment list is NULL", what);
-  SVLA_CHECK_ARG(in->nseg >= 1 && in->nseg <= MAX_SEG, "%s: 1..3 segments, got %d", what, in->nseg);
-  SVLA_CHECK_ARG(in->r >= 8 && in->r <= MAX_R && in->r % 8 == 0, "%s: rank must be a multiple of 8 in [8, 64], got %d",
-                 what, in->r);
-  SVLA_CHECK_ARG(in->ld > 0 && in->ld % 8 == 0, "%s: the small matrices' ld must be a positive multiple of 8, got %lld",
-                 what, (long long)in->ld);
-  S.nseg = in->nseg;
-  S.r = in->r;
-  S.R = (in->r + 31) / 32 * 32;
-  S.ld = in->ld;
-  for (int s = 0; s < MAX_SEG; ++s) {
-    S.p[s] = s < in->nseg ? (const bf16_t*)in->ptr[s] : nullptr;
-    SVLA_CHECK_ARG(s >= in->nseg || (S.p[s] != nullptr && aligned16(S.p[s])),
-                   "%s: segment %d pointer NULL or not 16-B aligned", what, s);
-  }
-  for (int s = 0; s <= MAX_SEG; ++s) S.st[s] = 0;
-  if (need_starts) {
-    SVLA_CHECK_ARG(in->start[0] == 0 && in->start[in->nseg] == extent, "%s: segment starts must run from 0 to %lld",
-                   what, (long long)extent);
-    for (int s = 0; s < in->nseg; ++s)
-      SVLA_CHECK_ARG(in->start[s + 1] > in->start[s] && in->start[s] % 16 == 0,
-                     "%s: segment starts must ascend and be multiples of 16", what);
-    for (int s = 0; s <= in->nseg; ++s) S.st[s] = in->start[s];
-  }
-  return SVLA_OK;
 }
 
 }  // namespace

@@ -512,18 +512,24 @@ class FP8DecodeWeights:
     moved, was modified in place (tensor version), or the optimizer stepped (WEIGHT_EPOCH).  `builds` counts this
     holder's (re)builds: the captured decode graphs hold raw pointers into the copies, so the decode state compares the
     model's sum of them (SpatialVLAForConditionalGeneration._fp8_decode_key); BUILDS counts those of every holder
-    (tests, tools)."""
+    (tests, tools).
+    frozen: the weights are the frozen base of unmerged LoRA adapters (enable_fp8_lora_decode), which no optimizer step
+    on A and B rewrites, so the copies do not follow WEIGHT_EPOCH (FP8Weights' rule: unless a weight sits in a
+    TrainEngine's flat buffers); a move or an in-place change rebuilds them as always."""
 
     BUILDS = [0]
 
-    def __init__(self):
+    def __init__(self, frozen: bool = False):
         self.mats = {}
         self.builds = 0
+        self.frozen = frozen
+
+    _epoch = FP8Weights._epoch
 
     def get(self, name, mats):
         """([q segments e4m3 [N_i, K]], [exponent segments uint8 [N_i, K/32]]) of cat(mats, 0): one segment, or for
         name == "gate_up" the gate rows and the up rows (the GEGLU pair)."""
-        key = (WEIGHT_EPOCH[0],) + tuple((m.data_ptr(), m._version) for m in mats)
+        key = (self._epoch(mats),) + tuple((m.data_ptr(), m._version) for m in mats)
         hit = self.mats.get(name)
         if hit is None or hit["key"] != key:
             q, sc = K.quant_mx_rows(FP8Weights._rows(mats))
@@ -725,10 +731,17 @@ def _lora_decode_ok(x_rows, k, weights, norm=False) -> bool:
             and K.lora_gemv_ok(x_rows, k, [w.shape[0] for w in weights], norm))
 
 
-def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora):
+def _lora_fp8_decode_ok(x_rows, k, weights) -> bool:
+    """Whether the projection half of an adapter decode step (after svla_lora_gemv_down) streams the e4m3 copy:
+    shapes svla_lora_gemv_mxfp8 takes, else svla_lora_gemv on the bf16 weights."""
+    return fp8_decode_ok(x_rows, k, weights) and K.lora_gemv_mxfp8_ok(x_rows, k, [w.shape[0] for w in weights])
+
+
+def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora, f8d=None):
     """gemma_attention_cached with an adapter on each of q, k, v, o: lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv),
     (Ao, Bo)).  Prefill: the uncached adapter forward's kernels (GemmaAttentionLoRAFn) with the RoPE + cache fill of
-    the base prefill; decode: the adapter GEMVs, or their composition."""
+    the base prefill; decode: the adapter GEMVs, or their composition.  f8d (enable_fp8_lora_decode): the adapter
+    GEMVs' projection half streams the e4m3 copies of the frozen base weights (svla_lora_gemv_mxfp8)."""
     r, s, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo) = lora
     ops = _lora_ops()
     if pre is not None:
@@ -752,7 +765,10 @@ def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
         if pre is not None:  # the norm pair in the prologue of the rank-r GEMV, which also stores x for the projection
             x = _empty(M, H, like=like)
         K.lora_gemv_down(x, [Aq, Ak, Av], r, t, norm=pre)
-        K.lora_gemv(x, [wq, wk, wv], t, [Bq, Bk, Bv], r, s, qkv)
+        if f8d is not None and _lora_fp8_decode_ok(M, H, [wq, wk, wv]):
+            K.lora_gemv_mxfp8(x, *f8d.get("qkv", [wq, wk, wv]), t, [Bq, Bk, Bv], r, s, qkv)
+        else:
+            K.lora_gemv(x, [wq, wk, wv], t, [Bq, Bk, Bv], r, s, qkv)
     else:
         if pre is not None:
             x = _empty(M, H, like=like)
@@ -779,7 +795,10 @@ def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     if p0 > 0 and _lora_decode_ok(M, qd, [wo]):
         t_o = _empty(M, R, like=like)
         K.lora_gemv_down(attn, [Ao], r, t_o)
-        K.lora_gemv(attn, [wo], t_o, [Bo], r, s, out)
+        if f8d is not None and _lora_fp8_decode_ok(M, qd, [wo]):
+            K.lora_gemv_mxfp8(attn, *f8d.get("o", [wo]), t_o, [Bo], r, s, out)
+        else:
+            K.lora_gemv(attn, [wo], t_o, [Bo], r, s, out)
     else:
         t_o = ops.down(attn, [Ao], r)
         K.linear_fwd(attn, [wo], out)
@@ -798,11 +817,13 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     decode step whose input x = rms(res + rms(y; w1); w2) is formed inside the q|k|v GEMV (h_out the new residual).
     lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections.
     f8d: the layer's FP8DecodeWeights (enable_fp8_decode) -- a decode step (p0 > 0) then streams the e4m3 copies of
-    q|k|v and o (svla_gemv_mxfp8); the prefill never reads them, and shapes the kernel refuses keep the bf16 GEMV."""
+    q|k|v and o (svla_gemv_mxfp8); the prefill never reads them, and shapes the kernel refuses keep the bf16 GEMV.
+    lora and f8d together (enable_fp8_lora_decode): each adapter GEMV pair of a decode step is svla_lora_gemv_down +
+    svla_lora_gemv_mxfp8."""
     if lora is not None:
         # the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term needs T
         # complete before the projection starts, which inside one launch would take a grid barrier
-        return _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora)
+        return _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora, f8d)
     if pre is not None:
         if p0 == 0:
             raise ValueError("gemma_attention_cached: the fused norm prologue is a decode-step path (p0 > 0)")
@@ -889,7 +910,9 @@ def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora
     down(gelu_tanh(gate x) * up x) with x = rms(h_out; w2).
     lora = (r, scaling, (Ag, Bg), (Au, Bu), (Ad, Bd)): unmerged adapters on the three projections.
     f8d: the layer's FP8DecodeWeights (enable_fp8_decode): the two-launch form on the e4m3 copies -- the norm-prologue
-    gate|up GeGLU GEMV, then the (split-K) down GEMV, both svla_gemv_mxfp8; not combined with `o` or `lora`."""
+    gate|up GeGLU GEMV, then the (split-K) down GEMV, both svla_gemv_mxfp8; not combined with `o`.  With `lora`
+    (enable_fp8_lora_decode) the adapter form keeps its four launches and svla_lora_gemv_mxfp8 streams the e4m3 copies
+    of gate|up and down."""
     if f8d is not None and lora is None and o is None:
         M, H = y.shape
         I = wg.shape[0]
@@ -916,11 +939,17 @@ def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora
             t = _empty(M, 2 * R, like=y)
             K.lora_gemv_down(x, [Ag, Au], r, t, norm=(res, y, w1, w2, eps1, eps2, h_out))
             hact, g, u = (_empty(M, I, like=y) for _ in range(3))
-            K.lora_gemv(x, [wg, wu], t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
+            if f8d is not None and _lora_fp8_decode_ok(M, H, [wg, wu]) and wu.shape[0] == I:
+                K.lora_gemv_mxfp8(x, *f8d.get("gate_up", [wg, wu]), t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
+            else:
+                K.lora_gemv(x, [wg, wu], t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
             t_d = _empty(M, R, like=y)
             K.lora_gemv_down(hact, [Ad], r, t_d)
             out = _empty(M, wd.shape[0], like=y)
-            K.lora_gemv(hact, [wd], t_d, [Bd], r, s, out)
+            if f8d is not None and _lora_fp8_decode_ok(M, I, [wd]):
+                K.lora_gemv_mxfp8(hact, *f8d.get("down", [wd]), t_d, [Bd], r, s, out)
+            else:
+                K.lora_gemv(hact, [wd], t_d, [Bd], r, s, out)
             return out
         K.add_rmsnorm2_fwd(res, y, w1, w2, eps1, eps2, h_out, x)
         return GemmaMLPLoRAFn.apply(x, wg, wu, wd, s, r, Ag, Bg, Au, Bu, Ad, Bd)
@@ -2117,10 +2146,12 @@ def lm_head_lora_decode_ok(h: torch.Tensor, r: int) -> bool:
             and K.lora_head_gemv_ok(h.shape[0], h.shape[1], r))
 
 
-def lm_head_lora_decode(h, w, target, cap, stash, scaling, r, A, B):
+def lm_head_lora_decode(h, w, target, cap, stash, scaling, r, A, B, f8d: Optional[FP8DecodeWeights] = None):
     """LMHeadCEFn's forward for a decode step (M <= 8 rows, no grad) with the lm_head adapter attached, in the launch
     count of the head without one: t = h A^T (svla_lora_gemv_down), then svla_lora_head_gemv streams lm_head once and
-    leaves the softcapped logits and the statistics, then svla_ce_finalize.  Returns (logits [M, V] view, loss)."""
+    leaves the softcapped logits and the statistics, then svla_ce_finalize.  f8d (enable_fp8_lora_decode): the e4m3
+    copy of lm_head is streamed instead (svla_lora_head_gemv_mxfp8) where that kernel takes the width.  Returns
+    (logits [M, V] view, loss)."""
     h = _c(h)
     M, V = h.shape[0], w.shape[0]
     t = _empty(M, K.lora_R(r), like=h)
@@ -2128,7 +2159,11 @@ def lm_head_lora_decode(h, w, target, cap, stash, scaling, r, A, B):
     logits_buf = _empty(M, K.round_up(V, 64), like=h)
     ntn = K.ceil_div(V, 128)
     stats = _empty(M, ntn, 3, dtype=F32, like=h)
-    K.lora_head_gemv(h, w, t, B, r, scaling, logits_buf, V, stats, cap)
+    if f8d is not None and K.lora_head_gemv_mxfp8_ok(M, h.shape[1], r):
+        (wq,), (ws,) = f8d.get("lm_head", [w])
+        K.lora_head_gemv_mxfp8(h, wq, ws, t, B, r, scaling, logits_buf, V, stats, cap)
+    else:
+        K.lora_head_gemv(h, w, t, B, r, scaling, logits_buf, V, stats, cap)
     lse = _empty(M, dtype=F32, like=h)
     argmax = _empty(M, dtype=torch.int64, like=h)
     loss_rows = _empty(M, dtype=F32, like=h)

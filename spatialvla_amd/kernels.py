@@ -1308,6 +1308,77 @@ def head_gemv_mxfp8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, logits:
                                          row_stats.data_ptr(), _stream()), "svla_head_gemv_mxfp8")
 
 
+def lora_gemv_mxfp8_ok(M: int, K: int, sizes: Sequence[int]) -> bool:
+    """Whether svla_lora_gemv_mxfp8 takes this decode-step projection: the shape gates of both parents (lora_gemv_ok
+    and gemv_mxfp8_ok; there is no norm-prologue form)."""
+    return lora_gemv_ok(M, K, sizes) and gemv_mxfp8_ok(M, K)
+
+
+def lora_gemv_mxfp8(x: torch.Tensor, wq: Sequence[torch.Tensor], ws: Sequence[torch.Tensor], t: torch.Tensor,
+                    mats: Sequence[torch.Tensor], r: int, scaling: float, out: torch.Tensor, geglu_out=None):
+    """Decode step with unmerged adapters over the e4m3 base copies: out = bf16(bf16(sum_b 2^X sum_{k in b} x q) +
+    bf16(scaling t_s B_s^T)) in one pass over the row segments wq / ws of gemv_mxfp8 (mats B_s [N_s, r], one per
+    segment -- a single segment under several B is split at their row counts --, t from lora_gemv_down; M <= 8,
+    K % 128 == 0).  geglu_out = (g, u) with wq = [gate, up]: the adapted g, u
+    are stored there and out = bf16(bf16(gelu_tanh(g)) u) (svla_lora_gemv_mxfp8)."""
+    for a, nm in ((x, "x"), (t, "t"), (out, "out")):
+        _chk_bf16(a, "lora_gemv_mxfp8 " + nm)
+    M, K = x.shape
+    if len(wq) == 1 and len(mats) > 1:  # one quantised matrix under several adapters (q|k|v): its row slices
+        _req(sum(b.shape[0] for b in mats) == wq[0].shape[0], "lora_gemv_mxfp8: the B rows must add up to the weight's")
+        wq, ws = list(wq[0].split([b.shape[0] for b in mats])), list(ws[0].split([b.shape[0] for b in mats]))
+    W, N = _mxfp8_rows(wq, ws, K, "lora_gemv_mxfp8")
+    _req(len(wq) == len(mats), "lora_gemv_mxfp8: one B per weight segment")
+    sizes = [q.shape[0] for q in wq]
+    for n, b in zip(sizes, mats):
+        _req(tuple(b.shape) == (n, r), "lora_gemv_mxfp8: weight / B shapes")
+    st, _ = _starts(sizes)
+    _req(t.shape[0] == M and t.shape[1] >= (len(mats) - 1) * lora_R(r) + r,
+         "lora_gemv_mxfp8: t is narrower than the slices")
+    segs = _lora_segs(mats, r, st + [N])
+    if geglu_out is not None:
+        _req(len(wq) == 2 and sizes[0] == sizes[1], "lora_gemv_mxfp8: GEGLU takes [gate, up]")
+        for a in geglu_out:
+            _chk_bf16(a, "lora_gemv_mxfp8 g/u")
+            _req(a.shape[0] >= M and a.shape[1] >= sizes[0], "lora_gemv_mxfp8: g/u shape")
+        _req(out.shape[0] >= M and out.shape[1] >= sizes[0], "lora_gemv_mxfp8: out shape")
+        e = _epi(L.EPI_GEGLU, out1=geglu_out[0], out2=geglu_out[1])
+    else:
+        _req(out.shape[0] >= M and out.shape[1] >= N, "lora_gemv_mxfp8: out shape")
+        e = _epi(L.EPI_STORE)
+    L.check(L.lib().svla_lora_gemv_mxfp8(M, N, K, x.data_ptr(), _ld(x), ctypes.byref(W), t.data_ptr(), _ld(t),
+                                         ctypes.byref(segs), float(scaling), out.data_ptr(), _ld(out), ctypes.byref(e),
+                                         _stream()), "svla_lora_gemv_mxfp8")
+
+
+def lora_head_gemv_mxfp8_ok(M: int, K: int, r: int) -> bool:
+    return lora_head_gemv_ok(M, K, r) and head_gemv_mxfp8_ok(M, K)
+
+
+def lora_head_gemv_mxfp8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, t: torch.Tensor, B: torch.Tensor, r: int,
+                         scaling: float, logits: torch.Tensor, N: int, row_stats: torch.Tensor, cap: float):
+    """The decode head on the e4m3 lm_head with an unmerged adapter, one pass over wq [N, K] (exponents ws [N, K/32]):
+    logits[:, :N] = softcap(bf16(bf16(product) + bf16(scaling t B^T))) and row_stats [M, ceil(N/128), 3], bitwise
+    lora_gemv_mxfp8 + softcap_ce_rows (svla_lora_head_gemv_mxfp8); t [M, >= r] from lora_gemv_down, B [N, r], M <= 8,
+    K % 128 == 0, K <= 4096."""
+    for a, nm in ((x, "x"), (t, "t"), (B, "B"), (logits, "logits")):
+        _chk_bf16(a, "lora_head_gemv_mxfp8 " + nm)
+    M, K = x.shape
+    _req(wq.is_cuda and wq.dtype == FP8 and tuple(wq.shape) == (N, K) and wq.stride(1) == 1,
+         f"lora_head_gemv_mxfp8: wq must be e4m3 [{N}, {K}]")
+    _req(ws.dtype == torch.uint8 and tuple(ws.shape) == (N, K // 32) and ws.stride(1) == 1,
+         f"lora_head_gemv_mxfp8: ws must be uint8 [{N}, {K // 32}]")
+    _req(tuple(B.shape) == (N, r) and B.stride(1) == 1, f"lora_head_gemv_mxfp8: B [{N}, {r}] with unit column stride")
+    _req(t.shape[0] == M and t.shape[1] >= r and logits.shape[0] == M and _ld(logits) >= N,
+         f"lora_head_gemv_mxfp8: t [{M}, >= {r}], logits [{M}, >= {N}]")
+    _req(row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == M * ceil_div(N, 128) * 3,
+         "lora_head_gemv_mxfp8: row_stats must be a contiguous fp32 [M, ceil(N/128), 3]")
+    L.check(L.lib().svla_lora_head_gemv_mxfp8(M, N, K, x.data_ptr(), _ld(x), wq.data_ptr(), wq.stride(0), ws.data_ptr(),
+                                              ws.stride(0), t.data_ptr(), _ld(t), B.data_ptr(), _ld(B), int(r),
+                                              float(scaling), float(cap), logits.data_ptr(), _ld(logits),
+                                              row_stats.data_ptr(), _stream()), "svla_lora_head_gemv_mxfp8")
+
+
 _lora_ws: dict = {}
 
 

@@ -396,6 +396,19 @@ class Gemma2Model(nn.Module):
     def fp8_decode(self) -> bool:
         return getattr(self.layers[0], "_svla_fp8_decode", None) is not None
 
+    def enable_fp8_lora_decode(self, enabled: bool = True):
+        """Weight-only MX fp8 decode under unmerged adapters (opt-in, on top of enable_lora_decode): the projection half
+        of every adapter GEMV pair of the fused decode step streams the e4m3 copy of its frozen base weight
+        (svla_lora_gemv_down + svla_lora_gemv_mxfp8).  The holders are their own attribute (frozen FP8DecodeWeights: an
+        optimizer step on A and B rebuilds nothing), so fp8_decode stays False; a sublayer without adapters keeps its
+        bf16 path, and so do the prefill and every other forward."""
+        for layer in self.layers:
+            layer._svla_fp8_lora_decode = Fn.FP8DecodeWeights(frozen=True) if enabled else None
+
+    @property
+    def fp8_lora_decode(self) -> bool:
+        return getattr(self.layers[0], "_svla_fp8_lora_decode", None) is not None
+
     def get_input_embeddings(self):
         return self.embed_tokens
 
@@ -500,19 +513,22 @@ class Gemma2Model(nn.Module):
                 pre = (h, m, po.weight, layer.input_layernorm.weight, po.eps, layer.input_layernorm.eps, res)
             la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))
             lm = _lora_args(_lora_of(mlp.gate_proj, mlp.up_proj, mlp.down_proj))
-            # weight-only fp8 decode (enable_fp8_decode): the layer's e4m3 copies, never together with adapters
+            # weight-only fp8 decode (enable_fp8_decode): the layer's e4m3 copies, never together with adapters --
+            # those take the holder of enable_fp8_lora_decode, in the sublayers that carry them
             f8d = getattr(layer, "_svla_fp8_decode", None) if la is None and lm is None else None
+            f8l = getattr(layer, "_svla_fp8_lora_decode", None)
             # o projection inside the MLP's launch (never with adapters: their term needs its own launch boundary)
             fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None and f8d is None
             a = Fn.gemma_attention_cached(x if i == 0 else None, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight,
                                           at.o_proj.weight, cos, sin, cache.key_cache[i], cache.value_cache[i],
                                           cache.kv_class, cache.seen_tokens, at.attn_cfg(B, Lq), pre=pre,
-                                          skip_o=fuse_o, lora=la, f8d=f8d)
+                                          skip_o=fuse_o, lora=la, f8d=f8d if la is None else f8l)
             pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
             h = torch.empty_like(res)
             m = Fn.gemma_mlp_decode(res, None if fuse_o else a, pa.weight, pf.weight, pa.eps, pf.eps, h,
                                     mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
-                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm, f8d=f8d)
+                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm,
+                                    f8d=f8d if lm is None else f8l)
         po = layers[-1].post_feedforward_layernorm
         res, x = torch.empty_like(h), torch.empty_like(h)
         Kn.add_rmsnorm2_fwd(h, m, po.weight, self.norm.weight, po.eps, self.norm.eps, res, x)
@@ -558,6 +574,18 @@ class Gemma2ForCausalLM(nn.Module):
         """Every FP8DecodeWeights of the model (the layers', then the head's); [] with the switch off."""
         hs = [getattr(l, "_svla_fp8_decode", None) for l in self.model.layers]
         hs.append(getattr(self, "_svla_fp8_decode_head", None))
+        return [h for h in hs if h is not None]
+
+    def enable_fp8_lora_decode(self, enabled: bool = True):
+        """Gemma2Model.enable_fp8_lora_decode, and the decode head on an e4m3 copy of lm_head: svla_lora_head_gemv_mxfp8
+        under an lm_head adapter, the head of enable_fp8_decode without one."""
+        self.model.enable_fp8_lora_decode(enabled)
+        self._svla_fp8_lora_decode_head = Fn.FP8DecodeWeights(frozen=True) if enabled else None
+
+    def fp8_lora_decode_holders(self):
+        """Every FP8DecodeWeights of enable_fp8_lora_decode (the layers', then the head's); [] with the switch off."""
+        hs = [getattr(l, "_svla_fp8_lora_decode", None) for l in self.model.layers]
+        hs.append(getattr(self, "_svla_fp8_lora_decode_head", None))
         return [h for h in hs if h is not None]
 
     def set_decoder(self, decoder):
@@ -606,7 +634,8 @@ class Gemma2ForCausalLM(nn.Module):
     def head(self, hidden_states, target, stash, decode: bool = False):
         """lm_head + softcap (reference :993-997) fused with the shifted CE; returns (logits2d, loss).  decode: the
         rows are a KV-cached decode step's (cache position > 0) -- with enable_fp8_decode they run on the e4m3 copy of
-        lm_head (M <= 8 no-grad rows; other shapes keep the bf16 head); the prefill's head never does."""
+        lm_head (M <= 8 no-grad rows; other shapes keep the bf16 head), with enable_fp8_lora_decode also under an lm_head
+        adapter (Fn.lm_head_lora_decode's e4m3 form); the prefill's head never does."""
         pwait = getattr(self, "_svla_param_wait", None)
         if pwait is not None:
             pwait("head")
@@ -617,10 +646,13 @@ class Gemma2ForCausalLM(nn.Module):
         adapter = () if ad is None else (ad.scaling, ad.r, ad.A, ad.B)
         h2d = hidden_states.reshape(-1, hidden_states.shape[-1])
         f8d = getattr(self, "_svla_fp8_decode_head", None) if decode and ad is None else None
+        f8l = getattr(self, "_svla_fp8_lora_decode_head", None) if decode else None  # enable_fp8_lora_decode
+        if ad is None and f8d is None:
+            f8d = f8l
         if f8d is not None and self.lm_head.weight.stride(1) == 1 and Fn.lm_head_fp8_decode_ok(h2d):
             return Fn.lm_head_fp8_decode(h2d, self.lm_head.weight, target, cap, stash, f8d)
         if ad is not None and Fn.lm_head_lora_decode_ok(h2d, ad.r):
             # a decode step's rows under the adapter: T, one pass over lm_head (svla_lora_head_gemv), finalize
-            return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter)
+            return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter, f8d=f8l)
         return Fn.LMHeadCEFn.apply(hidden_states.reshape(-1, hidden_states.shape[-1]), self.lm_head.weight, target,
                                    cap, stash, *adapter)

@@ -706,27 +706,67 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         walk; clear_decode_cache() forgets the stamp (a rebound parameter is a new tensor object)."""
         if not self.fp8_decode:
             return None
+        return self._fp8_copies_key("_svla_fp8_decode", self.language_model.fp8_decode_holders)
+
+    def _fp8_lora_decode_key(self):
+        """_fp8_decode_key for the copies of enable_fp8_lora_decode: None with that switch off, else (True, the count
+        of their (re)builds) after making every copy current."""
+        if not self.fp8_lora_decode:
+            return None
+        return self._fp8_copies_key("_svla_fp8_lora_decode", self.language_model.fp8_lora_decode_holders)
+
+    def _fp8_copies_key(self, attr, holders):
         lm = self.language_model
-        memo = self.__dict__.get("_svla_fp8_decode_memo")
-        if memo is not None and memo[1] == self._fp8_decode_stamp(memo[0]):
+        memo = self.__dict__.get(attr + "_memo")
+        if memo is not None and memo[1] == self._fp8_decode_stamp(memo[0], holders):
             return memo[2]
         with torch.no_grad():
             for layer in lm.model.layers:
-                f8d, at, mlp = layer._svla_fp8_decode, layer.self_attn, layer.mlp
+                f8d, at, mlp = getattr(layer, attr), layer.self_attn, layer.mlp
                 f8d.get("qkv", [at.q_proj.weight, at.k_proj.weight, at.v_proj.weight])
                 f8d.get("o", [at.o_proj.weight])
                 f8d.get("gate_up", [mlp.gate_proj.weight, mlp.up_proj.weight])
                 f8d.get("down", [mlp.down_proj.weight])
-            lm._svla_fp8_decode_head.get("lm_head", [lm.lm_head.weight])
-        key = (True, sum(h.builds for h in lm.fp8_decode_holders()))
+            getattr(lm, attr + "_head").get("lm_head", [lm.lm_head.weight])
+        key = (True, sum(h.builds for h in holders()))
         ws = [lin.weight for _, lin in self._lora_linears()] + [lm.lm_head.weight]
-        self.__dict__["_svla_fp8_decode_memo"] = (ws, self._fp8_decode_stamp(ws), key)
+        self.__dict__[attr + "_memo"] = (ws, self._fp8_decode_stamp(ws, holders), key)
         return key
 
-    def _fp8_decode_stamp(self, ws):
-        holders = self.language_model.fp8_decode_holders()
+    def _fp8_decode_stamp(self, ws, holders=None):
+        holders = (holders or self.language_model.fp8_decode_holders)()
         return (Fn.WEIGHT_EPOCH[0], sum(w._version for w in ws), sum(w.data_ptr() for w in ws),
                 sum(h.builds for h in holders))
+
+    @property
+    def fp8_lora_decode(self) -> bool:
+        return bool(self.language_model.model.fp8_lora_decode)
+
+    def enable_fp8_lora_decode(self, enabled: bool = True):
+        """Weight-only MX fp8 decode under unmerged LoRA adapters (opt-in, on top of enable_lora_decode): the decode
+        steps of predict_action, generate and forward(past_key_values=...) -- cache position > 0, at most 8 new token
+        rows -- stream OCP MX e4m3 copies of the frozen base q|k|v, o, gate|up and down weights and of lm_head, and the
+        rank-r adapter term is added in bf16 inside the same GEMV: every projection is svla_lora_gemv_down (unchanged,
+        bf16) + svla_lora_gemv_mxfp8, still 9 launches per layer; the head is svla_lora_head_gemv_mxfp8 under an
+        lm_head adapter (enable_lora_decode(True, emb_head=True)) and svla_head_gemv_mxfp8 without one.  The base
+        weights are frozen, so the copies (the 2.5 GiB of enable_fp8_decode, beside the bf16 weights) are made once, by
+        the first call, and survive every optimizer step on A and B and every load_lora() of the same set and rank,
+        which copies A and B in place; a base weight that moved or changed in place rebuilds its copy and drops the
+        captured graphs.  The prefill, svla_lora_embed_decode and every other forward are untouched (the prefill is
+        bitwise that of the model with the switch off); shapes either kernel family refuses, and
+        SVLA_LORA_DECODE_KERNELS=0, keep the bf16 adapter path.  fp8_decode stays False (the holders are separate), so
+        load_lora is not refused; enable_fp8_lora (the training step) is independent.  Needs adapters attached and
+        enable_lora_decode() on, else RuntimeError before any state changes.  Turned off, and the copies freed, by
+        enable_fp8_lora_decode(False), enable_lora_decode(False) and merge_lora().  Toggling drops the captured decode
+        states."""
+        if enabled and not self.has_lora:
+            raise RuntimeError("enable_fp8_lora_decode: no adapters attached (add_lora() / load_lora() first); a merged "
+                               "model streams its e4m3 weights through enable_fp8_decode()")
+        if enabled and not self.lora_decode:
+            raise RuntimeError("enable_fp8_lora_decode: the unmerged decode is off: call enable_lora_decode() first "
+                               "(the e4m3 copies replace the base weights of its adapter GEMVs)")
+        self.language_model.enable_fp8_lora_decode(enabled)
+        self.clear_decode_cache()
 
     @property
     def fp8_lora(self) -> bool:
@@ -831,7 +871,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         on the training forward's rank-r kernels, every decode-step projection as svla_lora_gemv_down + svla_lora_gemv
         (9 launches per layer; DESIGN.md section 4 "LoRA").  Off (the default): those entry points refuse adapters and
         ask for merge_lora().  The captured graphs read A and B in place, so an optimizer step on them needs no
-        re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on.
+        re-capture; toggling the switch drops the decode states.  This path is bf16 whether or not enable_fp8_lora is on
+        (enable_fp8_lora_decode puts the decode steps' base weights on e4m3 copies; turning this switch off clears it).
         With the "spatialvla-linear" set the prefill's SigLIP / Ego3D / projector run through their LoRA Functions under
         no_grad, inside the captured prefill graph; the decode steps never touch the vision side.  A modules_to_save
         spatial table needs nothing special (the graphs read the table in place).  With an adapter on
@@ -846,6 +887,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         if enabled and not permit:
             self._refuse_emb_head_decode("enable_lora_decode", permitted=False)
         self.language_model.enable_lora_decode(enabled)
+        if not enabled:
+            self.language_model.enable_fp8_lora_decode(False)  # it rides on the adapter GEMVs of this switch
         self.__dict__["_svla_lora_decode_emb_head"] = permit
         self.clear_decode_cache()
 
@@ -1008,6 +1051,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         if not self.has_lora:
             raise RuntimeError("merge_lora: no adapters attached")
         self.enable_fp8_lora(False)  # the e4m3 copies are of the unmerged base weights: the merge reads bf16
+        self.language_model.enable_fp8_lora_decode(False)  # and so are the decode copies
         for _, lin in self._lora_all_linears():
             ad = lin.lora
             w = lin.weight.data
@@ -1192,6 +1236,7 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         storage (TrainEngine's flat buffers, load_state_dict with assign, .to()) must call this."""
         self.__dict__["_svla_decode_states"] = {}
         self.__dict__.pop("_svla_fp8_decode_memo", None)
+        self.__dict__.pop("_svla_fp8_lora_decode_memo", None)
 
     @staticmethod
     def _prompt_positions(valid: torch.Tensor) -> torch.Tensor:
@@ -1217,9 +1262,10 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         # e4m3 weight copies, which the next eager forward after an optimizer step (WEIGHT_EPOCH) frees and rebuilds
         fp8 = any(getattr(l.mlp, "_svla_fp8", None) is not None for l in self.language_model.model.layers)
         # ... and to the LoRA adapters (rebound by TrainEngine / load_lora), with the path the switch selects
-        # ... and, with the weight-only fp8 decode, to its e4m3 copies: the switch and the copies' identity
+        # ... and, with the weight-only fp8 decode (alone or under adapters), to its e4m3 copies: the switch and the
+        # copies' identity
         wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1, self._adapter_key(),
-                self._fp8_decode_key())
+                self._fp8_decode_key(), self._fp8_lora_decode_key())
         if st is not None and st["wptr"] != wptr:  # weights were rebound since capture: the graphs are stale
             states.pop(key)
             st = None

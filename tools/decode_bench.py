@@ -228,6 +228,94 @@ def fp8_main(args):
         "data": "synthetic OXE-shaped prompt, random-init weights"}), flush=True)
 
 
+def lora_fp8_main(args):
+    """--lora R --fp8: ms per decode token of three variants in one process, alternating rounds (one model each, warmed
+    up and captured under its own setting, so the rounds only replay): the adapters merged into the bf16 weights, the
+    adapters unmerged on the bf16 adapter GEMVs (enable_lora_decode: the yardstick), and unmerged over the e4m3 copies
+    of the frozen base weights (enable_fp8_lora_decode).  Also the bytes a token streams in each, the share of the
+    greedy tokens on which the two unmerged legs agree (and, beside it, the two bf16 legs: random-init weights leave
+    small margins, so a greedy sequence rarely survives its first differing token), and the rel-L2 between the two
+    unmerged legs' logits of one teacher-forced decode step -- the quantisation error of the e4m3 base weights."""
+    from bench import build_model, make_batch
+    from spatialvla_amd import presets
+    dev = torch.device("cuda:0")
+    cfgd = json.loads(json.dumps(presets.spatialvla_4b()))
+    b = make_batch(cfgd, args.batch, 4321, dev)
+    P = int((b["token_type_ids"][0] == 0).sum())
+    inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
+    n_long = args.new_tokens + args.long
+    ends = "+emb" in args.lora_targets
+    models, toks, nbytes = {}, {}, {}
+    for name in ("merged", "adapters_bf16", "adapters_fp8"):
+        m = build_model(cfgd, dev).eval()
+        m.add_lora(args.lora, float(args.lora), target_modules=args.lora_targets, seed=1)
+        gen = torch.Generator(device="cpu").manual_seed(2)
+        with torch.no_grad():
+            for _, lin in m._lora_linears():  # a trained adapter: B away from its zero initialisation
+                lin.lora.B.copy_((torch.randn(lin.lora.B.shape, generator=gen) * 0.01).to(torch.bfloat16))
+            if ends:  # the Embedding adapter starts at A = 0, the lm_head adapter at B = 0
+                ad = m.spatial_embed_tokens.lora
+                ad.A.copy_((torch.randn(ad.A.shape, generator=gen) * 0.01).to(torch.bfloat16))
+                ad = getattr(m.language_model.lm_head, "lora", None)
+                if ad is not None:
+                    ad.B.copy_((torch.randn(ad.B.shape, generator=gen) * 0.01).to(torch.bfloat16))
+        lm = m.language_model
+        ads = [lin.lora for _, lin in m._lora_linears()] + [a for a in (getattr(lm.lm_head, "lora", None),) if a]
+        adapters = sum(t.numel() * t.element_size() for ad in ads for t in (ad.A, ad.B))
+        norms = sum(p.numel() * p.element_size() for n, p in lm.model.named_parameters() if "norm" in n)
+        base = (sum(lin.weight.numel() * lin.weight.element_size() for _, lin in m._lora_linears())
+                + lm.lm_head.weight.numel() * lm.lm_head.weight.element_size())
+        if name == "merged":
+            m.merge_lora()
+            adapters = 0
+        else:
+            m.enable_lora_decode(True, emb_head=ends)
+            if name == "adapters_fp8":
+                m.enable_fp8_lora_decode()
+        with torch.no_grad():  # warm-up under the variant's setting: every graph this model replays is captured here
+            m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1)
+            toks[name] = m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1)
+        if name == "adapters_fp8":
+            base = sum(h.nbytes() for h in lm.fp8_lora_decode_holders())
+        nbytes[name] = base + norms + adapters
+        models[name] = m
+    rounds = []
+    with torch.no_grad():
+        for _ in range(args.rounds):
+            row = {}
+            for name, m in models.items():
+                t1, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1), args.reps)
+                tl, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1),
+                              max(3, args.reps // 2))
+                row[name] = {"ms_prefill_plus_first": round(t1, 2), "ms_per_decode_token": round((tl - t1) / (n_long - 1), 4)}
+            rounds.append(row)
+    per = {n: [r[n]["ms_per_decode_token"] for r in rounds] for n in models}
+    best = {n: min(v) for n, v in per.items()}
+    agree = float((toks["adapters_bf16"] == toks["adapters_fp8"]).float().mean())
+    agree_bf16 = float((toks["adapters_bf16"] == toks["merged"]).float().mean())
+
+    def step_logits(m):  # the prompt, then the bf16 leg's first token through the KV-cached step
+        with torch.no_grad():
+            cache = m(**inputs, use_cache=True).past_key_values
+            return m(input_ids=toks["adapters_bf16"][:, :1], past_key_values=cache).logits.float()
+
+    lb, lf = step_logits(models["adapters_bf16"]), step_logits(models["adapters_fp8"])
+    step_rel = float((lf - lb).norm() / lb.norm())
+    print(json.dumps({
+        "metric": "SpatialVLA-4B greedy decode latency with unmerged LoRA adapters, bf16 against e4m3 base weights",
+        "unit": "ms", "batch": args.batch, "r": args.lora, "lora_targets": args.lora_targets, "prompt_tokens": P,
+        "decode_tokens_timed": n_long - 1, "rounds": rounds,
+        "ms_per_decode_token_min_max": {n: [min(v), max(v)] for n, v in per.items()},
+        "bytes_per_token": nbytes,
+        "achieved_GBps": {n: round(nbytes[n] / (best[n] * 1e-3) / 1e9, 1) for n in models},
+        "e4m3_copies_bytes": sum(h.nbytes() for h in models["adapters_fp8"].language_model.fp8_lora_decode_holders()),
+        "greedy_tokens": n_long, "unmerged_tokens_agree_share": round(agree, 4),
+        "bf16_unmerged_vs_merged_tokens_agree_share": round(agree_bf16, 4),
+        "decode_step_logits_rel_l2_fp8_vs_bf16_unmerged": round(step_rel, 5),
+        "decode_graphs": bool(models["merged"].decode_graphs),
+        "data": "synthetic OXE-shaped prompt, random-init weights and adapters"}), flush=True)
+
+
 VARIANTS = "merged,adapters_kernels,adapters_composed"
 
 
@@ -249,8 +337,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="--lora / --fp8: alternating rounds")
     ap.add_argument("--fp8", action="store_true",
                     help="bf16 against the weight-only MX fp8 decode (enable_fp8_decode), alternating rounds, bytes per "
-                         "token, token agreement and a per-kernel table")
+                         "token, token agreement and a per-kernel table; with --lora R: merged bf16, unmerged on the "
+                         "bf16 adapter GEMVs and unmerged over the e4m3 copies (enable_fp8_lora_decode)")
     args = ap.parse_args()
+    if args.lora and args.fp8:
+        return lora_fp8_main(args)
     if args.lora:
         return lora_main(args)
     if args.fp8:
