@@ -423,6 +423,33 @@ int svla_lora_head_gemv_mxfp8(int64_t M, int64_t N, int64_t K, const void* x, in
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batched decode (csrc/decode_batched.hip): the small projections (q|k|v, o) of a KV-cached step over more than 8 token
+ * rows (parallel environments, offline labelling; the step of model/modeling_spatialvla.py:440-492 with a batch), where
+ * the VALU GEMVs stop (M <= 8) and the tiled GEMMs run mostly zero-filled 64-row tiles.
+ * ---------------------------------------------------------------------------------------- */
+/* A bf16 weight W [N][K] as up to 3 row segments (q|k|v), separately allocated: segment s covers rows
+ * [start[s], start[s+1]), start[0] = 0, start[nseg] = N; w[s] its rows [N_s][ldw], K contiguous, 16-B aligned,
+ * ldw % 8 == 0.  Segment starts need no alignment. */
+typedef struct {
+  const void* w[3];
+  int64_t start[4];
+  int64_t ldw;
+  int32_t nseg;
+  int32_t _pad;
+} svla_bf16_rows;
+/* y[m,n] = bf16( sum_k x[m,k] W[n,k] ), fp32 accumulation on v_mfma_f32_16x16x32_bf16, for 1 <= M <= 64 rows of bf16
+ * x [M][ldx] (16-B aligned, ldx % 8 == 0), any N >= 1, K % 32 == 0 (no upper bound), y [M][ldy] (16-B aligned,
+ * ldy % 8 == 0, ldy >= N; columns >= N are never written).  The weight is streamed once by 16-B non-temporal loads
+ * straight into the MFMA's fragment registers; a workgroup owns 16 output columns and its waves split K, summed through
+ * LDS in wave order (no workspace, no atomics).  Plain store only.
+ * Batch invariance: the tiling and the K split depend on (N, K) only, so row m of y is bit-identical for every M and
+ * every position of that row among the M rows.
+ * M outside [1, 64], K % 32 != 0, or a misaligned pointer or leading dimension is refused (svla_last_error) before any
+ * launch. */
+int svla_gemm_skinny(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx, const svla_bf16_rows* W, void* y,
+                     int64_t ldy, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Attention.  Reference: eager_attention_forward (model/modeling_gemma2.py:169-195) selected via
  * GEMMA2_ATTENTION_FUNCTION (:317-322) with the prefix-LM additive mask of
  * _update_causal_mask (model/modeling_spatialvla.py:258-306) and Gemma2 RoPE

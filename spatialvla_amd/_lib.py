@@ -86,6 +86,10 @@ class MxFp8Rows(ctypes.Structure):
                 ("nseg", c_i32), ("_pad", c_i32)]
 
 
+class Bf16Rows(ctypes.Structure):
+    _fields_ = [("w", c_vp * 3), ("start", c_i64 * 4), ("ldw", c_i64), ("nseg", c_i32), ("_pad", c_i32)]
+
+
 LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
 LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU, LORA_EPI_GELU, LORA_EPI_RESID, LORA_EPI_SCALE = 0, 1, 2, 3, 4, 5
 
@@ -141,6 +145,7 @@ SIGNATURES = {
                                      ctypes.POINTER(LoraSegs), c_f32, c_vp, c_i64, ctypes.POINTER(Epilogue), c_vp]),
     "svla_lora_head_gemv_mxfp8": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
                                           c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
+    "svla_gemm_skinny": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(Bf16Rows), c_vp, c_i64, c_vp]),
     "svla_attn_fwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_vp]),
     "svla_attn_bwd": (c_i32, [ctypes.POINTER(AttnArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_i64, c_vp, c_vp]),

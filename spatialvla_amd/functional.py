@@ -806,9 +806,32 @@ def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     return out
 
 
+# Batched decode (enable_batched_decode): the window of new token rows B * Lq of a KV-cached step whose q|k|v and o
+# projections run on svla_gemm_skinny.  Below it the GEMVs run (<= 8 rows); 64 is the kernel's limit.  The same-process
+# A/B at 4B (tools/decode_bench.py --batched, profiles/batched_decode_ab.txt) has the switch ahead by more than the
+# rounds' spread at 16, 32, 48 and 64 rows, one point per count of 16-row tiles, so the whole range is routed.
+BATCHED_DECODE_MIN_ROWS = 9
+BATCHED_DECODE_MAX_ROWS = 64
+
+
+def batched_decode_ok(enabled: bool, rows: int, seen_tokens: int, grad_enabled: bool, bf16: bool = True,
+                      adapters: bool = False, fp8_decode: bool = False, fp8_projections: bool = False,
+                      widths=()) -> bool:
+    """Whether a KV-cached step takes the batched decode path (q|k|v and o on svla_gemm_skinny), and the one place
+    that states its exclusions: the switch is on, the step is a decode step (seen_tokens > 0) without grad, it adds
+    BATCHED_DECODE_MIN_ROWS..BATCHED_DECODE_MAX_ROWS token rows, the base weights are bf16, no adapters are attached
+    and no fp8 switch (enable_fp8_decode, enable_fp8_lora_decode, enable_fp8_projections) is on; `widths`: the
+    reduction widths of the two projections, each a multiple of 32.  Everything else keeps the path it had.  Pure
+    Python: nothing here touches a device."""
+    return bool(enabled and seen_tokens > 0 and not grad_enabled
+                and BATCHED_DECODE_MIN_ROWS <= rows <= BATCHED_DECODE_MAX_ROWS
+                and bf16 and not adapters and not fp8_decode and not fp8_projections
+                and all(k >= 32 and k % 32 == 0 for k in widths))
+
+
 @torch.no_grad()
 def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg: GemmaAttnCfg,
-                           pre=None, skip_o=False, lora=None, f8d=None):
+                           pre=None, skip_o=False, lora=None, f8d=None, batched=False):
     """Gemma2Attention.forward with a KV cache (modeling_gemma2.py:364-413, cache update :387-395), inference
     only.  x holds the cfg.L new tokens of each of the cfg.B sequences, at absolute positions p0 .. p0+L-1;
     their rotated k and v are written into rows p0.. of k_cache/v_cache ([B, capacity, Hkv*D]).  The prefill
@@ -819,7 +842,11 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     f8d: the layer's FP8DecodeWeights (enable_fp8_decode) -- a decode step (p0 > 0) then streams the e4m3 copies of
     q|k|v and o (svla_gemv_mxfp8); the prefill never reads them, and shapes the kernel refuses keep the bf16 GEMV.
     lora and f8d together (enable_fp8_lora_decode): each adapter GEMV pair of a decode step is svla_lora_gemv_down +
-    svla_lora_gemv_mxfp8."""
+    svla_lora_gemv_mxfp8.
+    batched (enable_batched_decode, batched_decode_ok): a decode step whose q|k|v and o projections are
+    svla_gemm_skinny; never with pre, lora or f8d."""
+    if batched and (p0 == 0 or pre is not None or lora is not None or f8d is not None):
+        raise ValueError("gemma_attention_cached: batched is a plain bf16 decode step (p0 > 0, no pre / lora / f8d)")
     if lora is not None:
         # the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term needs T
         # complete before the projection starts, which inside one launch would take a grid barrier
@@ -842,7 +869,9 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
         # the kernels read table row b*Lq+t (per-sequence positions), so a shared table is repeated per sequence
         if cos.shape[0] != B * Lq:
             cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
-        if f8d is not None and fp8_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
+        if batched:
+            K.gemm_skinny(x, [wq, wk, wv], qkv)
+        elif f8d is not None and fp8_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
             K.gemv_mxfp8(x, *f8d.get("qkv", [wq, wk, wv]), qkv, norm=pre)
         elif pre is not None:
             K.gemv_rmsnorm2(*pre, [wq, wk, wv], qkv)
@@ -875,7 +904,9 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     if skip_o:  # the caller runs the o projection (gemma_mlp_decode with o=(attn, wo): inside its launch)
         return attn
     out = _empty(M, wo.shape[0], like=like)
-    if p0 > 0 and f8d is not None and fp8_decode_ok(M, qd, [wo]):
+    if batched:
+        K.gemm_skinny(attn, [wo], out)
+    elif p0 > 0 and f8d is not None and fp8_decode_ok(M, qd, [wo]):
         K.gemv_mxfp8(attn, *f8d.get("o", [wo]), out)
     else:
         K.linear_fwd(attn, [wo], out)

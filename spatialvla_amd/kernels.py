@@ -1690,3 +1690,36 @@ def conv2d_cl(x: torch.Tensor, w_khwc: torch.Tensor, bias: Optional[torch.Tensor
         a.workspace, a.ws_bytes = ws.data_ptr(), ws.numel()
     L.check(L.lib().svla_conv2d_nhwc(ctypes.byref(a), _stream()), "svla_conv2d_nhwc")
     return out
+
+
+# ------------------------------------------------------------------------- batched decode (decode_batched.hip)
+GEMM_SKINNY_MAX_M = 64  # token rows of svla_gemm_skinny
+
+
+def gemm_skinny_ok(M: int, K: int) -> bool:
+    """Whether svla_gemm_skinny takes this projection: 1 <= M <= 64 rows, K % 32 == 0."""
+    return 1 <= M <= GEMM_SKINNY_MAX_M and K >= 32 and K % 32 == 0
+
+
+def gemm_skinny(x: torch.Tensor, ws: Sequence[torch.Tensor], out: torch.Tensor, M: Optional[int] = None):
+    """Batched decode projection: out[:M, :N] = bf16(x W^T) over the row segments ws (bf16 [N_i, K], separately
+    allocated, one row stride), 1 <= M <= 64, K % 32 == 0, on the weight-streaming MFMA kernel (svla_gemm_skinny).
+    Row m of the result does not depend on M or on the row's position.  M overrides x.shape[0] (the argument checks
+    are the library's)."""
+    _chk_bf16(x, "gemm_skinny x")
+    _chk_bf16(out, "gemm_skinny out")
+    _req(1 <= len(ws) <= 3, "gemm_skinny: 1..3 weight segments")
+    K = x.shape[1]
+    W = L.Bf16Rows()
+    n = 0
+    for i, w in enumerate(ws):
+        _chk_bf16(w, f"gemm_skinny weight {i}")
+        _req(w.dim() == 2 and w.shape[1] == K and w.stride(1) == 1 and w.stride(0) == ws[0].stride(0),
+             f"gemm_skinny: segment {i} must be bf16 [N_i, {K}] rows of one stride")
+        W.w[i], W.start[i] = w.data_ptr(), n
+        n += w.shape[0]
+    W.start[len(ws)] = n
+    W.ldw, W.nseg = ws[0].stride(0), len(ws)
+    M = x.shape[0] if M is None else int(M)
+    L.check(L.lib().svla_gemm_skinny(M, n, K, x.data_ptr(), _ld(x), ctypes.byref(W), out.data_ptr(), _ld(out),
+                                     _stream()), "svla_gemm_skinny")

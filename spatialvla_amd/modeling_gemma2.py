@@ -376,6 +376,8 @@ class Gemma2Model(nn.Module):
         self.gradient_checkpointing = False
         # KV-cached forward with unmerged LoRA adapters (enable_lora_decode): off = refuse, as before the switch existed
         self.lora_decode = False
+        # KV-cached steps of more than 8 rows with q|k|v and o on svla_gemm_skinny (enable_batched_decode)
+        self.batched_decode = False
 
     def enable_lora_decode(self, enabled: bool = True):
         """Let the KV-cached forward (prefill and decode steps) run with unmerged LoRA adapters attached: each adapted
@@ -408,6 +410,30 @@ class Gemma2Model(nn.Module):
     @property
     def fp8_lora_decode(self) -> bool:
         return getattr(self.layers[0], "_svla_fp8_lora_decode", None) is not None
+
+    def enable_batched_decode(self, enabled: bool = True):
+        """Batched decode (opt-in, default off): a KV-cached step that adds more than 8 token rows (B * Lq inside
+        Fn.BATCHED_DECODE_MIN_ROWS..MAX_ROWS) runs q|k|v and o on svla_gemm_skinny, the weight-streaming MFMA kernel
+        whose rows are bit-identical for every batch size and row position.  gate|up, down, lm_head, the norms, the
+        attention, the cache and the greedy bookkeeping are what they were.  Fn.batched_decode_ok states what is
+        excluded; every excluded step keeps the path it had."""
+        self.batched_decode = bool(enabled)
+
+    def _batched_decode_ok(self, rows: int, seen_tokens: int) -> bool:
+        if not self.batched_decode:  # nothing is scanned on the paths the switch leaves alone
+            return False
+        layers = self.layers[: self.config.num_hidden_layers]
+        projs = [p for l in layers for p in (l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj,
+                                            l.self_attn.o_proj)]
+        at = layers[0].self_attn
+        return Fn.batched_decode_ok(
+            True, rows, seen_tokens, torch.is_grad_enabled(),
+            bf16=all(p.weight.dtype == torch.bfloat16 and p.weight.stride(1) == 1 for p in projs),
+            adapters=any(getattr(p, "lora", None) is not None for l in layers
+                         for p in (l.self_attn.q_proj, l.mlp.gate_proj)),  # _lora_of: all of a sublayer or none
+            fp8_decode=self.fp8_decode or self.fp8_lora_decode,
+            fp8_projections=any(getattr(l.mlp, "_svla_fp8", None) is not None for l in layers),
+            widths=(at.q_proj.weight.shape[1], at.o_proj.weight.shape[1]))
 
     def get_input_embeddings(self):
         return self.embed_tokens
@@ -479,6 +505,8 @@ class Gemma2Model(nn.Module):
                 and H <= Kn.GEMV_NORM_MAX_K and H % 8 == 0
                 and (self.fp8_decode or all(getattr(l.mlp, "_svla_fp8", None) is None for l in layers))):
             return self._decode_fused(res, shp, rope, cache)
+        if self._batched_decode_ok(res.shape[0], cache.seen_tokens):
+            return self._decode_batched(res, shp, rope, cache)
         x = layers[0].input_layernorm(res)
         for i, layer in enumerate(layers):
             a = layer.self_attn(x.view(shp), attention_mask, rope, cache).reshape(-1, H)
@@ -493,6 +521,29 @@ class Gemma2Model(nn.Module):
         cache.seen_tokens += shp[1]
         return x.view(shp)
 
+
+    def _decode_batched(self, res, shp, rope, cache):
+        """A batched decode step (enable_batched_decode, Fn.batched_decode_ok): _forward_cached's unfused loop with
+        q|k|v and o on svla_gemm_skinny; everything else in it is that loop's."""
+        layers = self.layers[: self.config.num_hidden_layers]
+        B, Lq = shp[0], shp[1]
+        cos, sin = rope
+        x = layers[0].input_layernorm(res)
+        for i, layer in enumerate(layers):
+            at, mlp = layer.self_attn, layer.mlp
+            a = Fn.gemma_attention_cached(x, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight, at.o_proj.weight,
+                                          cos, sin, cache.key_cache[i], cache.value_cache[i], cache.kv_class,
+                                          cache.seen_tokens, at.attn_cfg(B, Lq), batched=True)
+            pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
+            h, x = torch.empty_like(res), torch.empty_like(res)
+            Kn.add_rmsnorm2_fwd(res, a, pa.weight, pf.weight, pa.eps, pf.eps, h, x)
+            m = mlp(x).reshape(-1, x.shape[-1])
+            nxt = layers[i + 1].input_layernorm if i + 1 < len(layers) else self.norm
+            po = layer.post_feedforward_layernorm
+            res, x = torch.empty_like(res), torch.empty_like(res)
+            Kn.add_rmsnorm2_fwd(h, m, po.weight, nxt.weight, po.eps, nxt.eps, res, x)
+        cache.seen_tokens += shp[1]
+        return x.view(shp)
 
     def _decode_fused(self, res, shp, rope, cache):
         """A decode step (<= 8 new tokens) with every norm pair between sublayers inside the next projection's GEMV
@@ -569,6 +620,14 @@ class Gemma2ForCausalLM(nn.Module):
         """Gemma2Model.enable_fp8_decode, and the decode head (head(decode=True)) on an e4m3 copy of lm_head."""
         self.model.enable_fp8_decode(enabled)
         self._svla_fp8_decode_head = Fn.FP8DecodeWeights() if enabled else None
+
+    def enable_batched_decode(self, enabled: bool = True):
+        """Gemma2Model.enable_batched_decode; the head is not involved."""
+        self.model.enable_batched_decode(enabled)
+
+    @property
+    def batched_decode(self) -> bool:
+        return bool(getattr(self.model, "batched_decode", False))
 
     def fp8_decode_holders(self):
         """Every FP8DecodeWeights of the model (the layers', then the head's); [] with the switch off."""

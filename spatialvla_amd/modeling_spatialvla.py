@@ -693,6 +693,21 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         self.language_model.enable_fp8_decode(enabled)
         self.clear_decode_cache()
 
+    @property
+    def batched_decode(self) -> bool:
+        return bool(self.language_model.batched_decode)
+
+    def enable_batched_decode(self, enabled: bool = True):
+        """Batched decode (opt-in, default off), for callers that step many sequences at once: the decode steps of
+        predict_action, generate and forward(past_key_values=...) that add more than 8 token rows (batch x new tokens,
+        functional.BATCHED_DECODE_MIN_ROWS..MAX_ROWS) run the Gemma2 q|k|v and o projections on svla_gemm_skinny,
+        which streams each bf16 weight once into v_mfma_f32_16x16x32_bf16 fragments.  In these products a sequence's
+        rows are bit-identical whatever the batch size and wherever the sequence sits in the batch.  Everything else
+        in the step is unchanged, and functional.batched_decode_ok states which steps are excluded (each keeps the
+        path it had).  Toggling drops the captured decode states."""
+        self.language_model.enable_batched_decode(enabled)
+        self.clear_decode_cache()
+
     def _refuse_lora_under_fp8_decode(self, what: str):
         if self.fp8_decode:
             raise RuntimeError(f"{what}: weight-only fp8 decode is on (enable_fp8_decode): call "
@@ -1266,6 +1281,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         # copies' identity
         wptr = (self.language_model.lm_head.weight.data_ptr(), Fn.WEIGHT_EPOCH[0] if fp8 else -1, self._adapter_key(),
                 self._fp8_decode_key(), self._fp8_lora_decode_key())
+        if self.batched_decode:  # ... and the batched-decode switch selects other kernels: a sixth element while on
+            wptr += ("batched",)
         if st is not None and st["wptr"] != wptr:  # weights were rebound since capture: the graphs are stale
             states.pop(key)
             st = None

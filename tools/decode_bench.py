@@ -17,6 +17,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
+def algorithmic_bytes_per_token_step(lm):
+    """The bf16 bytes a decode step streams: every Gemma2 layer weight, the final norm and lm_head once (the
+    decode_roofline.algorithmic_bytes_per_token_step of the default mode's JSON line)."""
+    n = sum(p.numel() * p.element_size() for p in lm.model.layers.parameters())
+    n += lm.lm_head.weight.numel() * lm.lm_head.weight.element_size()
+    return n + lm.model.norm.weight.numel() * lm.model.norm.weight.element_size()
+
+
 def timed(fn, reps):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     times = []
@@ -316,6 +324,121 @@ def lora_fp8_main(args):
         "data": "synthetic OXE-shaped prompt, random-init weights and adapters"}), flush=True)
 
 
+def batched_main(args):
+    """--batched: ms per decode step with the batched-decode switch off and on (enable_batched_decode) in one process,
+    graph replay, alternating rounds (one model each, warmed up and captured under its own setting, so the rounds only
+    replay) at every batch of --batches; a batch of at most 8 rows runs the switch-off model only (the GEMV path, which
+    the switch does not touch: the neighbouring point).  Reports ms per step, tokens/s, achieved GB/s against the bf16
+    bytes a step streams (algorithmic_bytes_per_token_step) and the rounds' spread, and, at --table-rows rows, the
+    time per launch of the five projections of a step on the general GEMM and, for the two the switch routes (q|k|v,
+    o), on svla_gemm_skinny, each swept over the 26 layers' own weights inside one captured graph (device time, cold
+    weights as in the step)."""
+    from bench import build_model, make_batch
+    from spatialvla_amd import functional as Fn, kernels as K, presets
+    dev = torch.device("cuda:0")
+    cfgd = json.loads(json.dumps(presets.spatialvla_4b()))
+    n_long = args.new_tokens + args.long
+    models = {"off": build_model(cfgd, dev).eval(), "on": build_model(cfgd, dev).eval()}
+    models["on"].enable_batched_decode()
+    for m in models.values():  # the depth estimator's convolutions take at most 2 GiB of input: 8 images a call
+        m.predict_depth = lambda pv, _f=m.predict_depth: torch.cat([_f(pv[i:i + 8]) for i in range(0, pv.shape[0], 8)], 0)
+    lm = models["off"].language_model
+    wbytes = algorithmic_bytes_per_token_step(lm)
+    results = []
+    for batch in [int(v) for v in args.batches.split(",") if v and v != "none"]:
+        b = make_batch(cfgd, batch, 4321, dev)
+        P = int((b["token_type_ids"][0] == 0).sum())
+        inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
+        names = ["off", "on"] if batch >= Fn.BATCHED_DECODE_MIN_ROWS else ["off"]
+        toks, rounds = {}, []
+        with torch.no_grad():
+            for name in names:  # warm-up: every graph the rounds replay is captured here
+                models[name].predict_action(inputs, max_new_tokens=1, eos_token_id=-1)
+                toks[name] = models[name].predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1)
+            for _ in range(args.rounds):
+                row = {}
+                for name in names:
+                    m = models[name]
+                    t1, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=1, eos_token_id=-1), args.reps)
+                    tl, _ = timed(lambda: m.predict_action(inputs, max_new_tokens=n_long, eos_token_id=-1), args.reps)
+                    row[name] = round((tl - t1) / (n_long - 1), 4)
+                rounds.append(row)
+        per = {n: [r[n] for r in rounds] for n in names}
+        med = {n: sorted(v)[len(v) // 2] for n, v in per.items()}
+        res = {"batch": batch, "prompt_tokens": P, "decode_steps_timed": n_long - 1, "rounds_ms_per_step": rounds,
+               "ms_per_step_median": med, "ms_per_step_min_max": {n: [min(v), max(v)] for n, v in per.items()},
+               "tokens_per_s": {n: round(1000.0 * batch / v, 1) for n, v in med.items()},
+               "achieved_GBps": {n: round(wbytes / (v * 1e-3) / 1e9, 1) for n, v in med.items()}}
+        if "on" in names:
+            spread = max(max(v) - min(v) for v in per.values())
+            res["spread_ms"] = round(spread, 4)
+            res["on_minus_off_ms"] = round(med["on"] - med["off"], 4)
+            res["on_beats_off_by_more_than_spread"] = bool(med["off"] - med["on"] > spread)
+            res["tokens_agree_share"] = round(float((toks["on"] == toks["off"]).float().mean()), 4)
+        results.append(res)
+        for m in models.values():
+            m.clear_decode_cache()
+        print(json.dumps(res), file=sys.stderr, flush=True)
+
+    # per-launch table: the five routed projections at --table-rows rows, one launch per layer inside one graph
+    tables = {}
+    for M in [int(v) for v in str(args.table_rows).split(",")]:
+        tables[str(M)] = _batched_table(args, K, lm, M, dev)
+    print(json.dumps({
+        "metric": "SpatialVLA-4B batched greedy decode, enable_batched_decode off against on", "unit": "ms per decode step",
+        "algorithmic_bytes_per_token_step": wbytes, "window_rows": [Fn.BATCHED_DECODE_MIN_ROWS, Fn.BATCHED_DECODE_MAX_ROWS],
+        "batches": results, "per_launch_us_by_rows": tables,
+        "per_launch_note": "device time per launch: one launch per layer over that layer's own weights (lm_head: one "
+                           "launch), the sweep captured in one graph and replayed; general_gemm = svla_gemm_bf16 "
+                           "through linear_fwd / linear_geglu_fwd, gemm_skinny = the two projections the switch routes",
+        "decode_graphs": bool(models["off"].decode_graphs), "dtype": "bf16",
+        "data": "synthetic OXE-shaped prompt, random-init weights"}), flush=True)
+
+
+def _batched_table(args, K, lm, M, dev):
+    """The five projections of a step at M rows on the general GEMM, q|k|v and o also on svla_gemm_skinny: us per launch."""
+    tc = lm.config
+    H, I, V = tc.hidden_size, tc.intermediate_size, lm.lm_head.weight.shape[0]
+    qd, kd = tc.num_attention_heads * tc.head_dim, tc.num_key_value_heads * tc.head_dim
+    g = torch.Generator(device="cpu").manual_seed(3)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).to(dev)  # noqa: E731
+    x, attn, hin = rnd(M, H), rnd(M, qd), rnd(M, I)
+    qkv, out = (torch.empty(M, n, dtype=torch.bfloat16, device=dev) for n in (qd + 2 * kd, H))
+    hact, gbuf, ubuf = (torch.empty(M, I, dtype=torch.bfloat16, device=dev) for _ in range(3))
+    logits = torch.empty(M, K.round_up(V, 64), dtype=torch.bfloat16, device=dev)
+    layers = list(lm.model.layers)
+
+    def sweep(fn, over):
+        def run():
+            for l in over:
+                fn(l)
+        with torch.no_grad():
+            run()
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                run()
+            gr.replay()
+            t, _ = timed(gr.replay, max(5, args.reps))
+        return round(t * 1e3 / len(over), 2)
+
+    att = lambda l: l.self_attn  # noqa: E731
+    table = {
+        "general_gemm": {
+            "qkv_us": sweep(lambda l: K.linear_fwd(x, [att(l).q_proj.weight, att(l).k_proj.weight, att(l).v_proj.weight],
+                                                   qkv), layers),
+            "o_us": sweep(lambda l: K.linear_fwd(attn, [att(l).o_proj.weight], out), layers),
+            "gate_up_geglu_us": sweep(lambda l: K.linear_geglu_fwd(x, l.mlp.gate_proj.weight, l.mlp.up_proj.weight, hact,
+                                                                   gbuf, ubuf), layers),
+            "down_us": sweep(lambda l: K.linear_fwd(hin, [l.mlp.down_proj.weight], out), layers),
+            "lm_head_us": sweep(lambda _l: K.linear_fwd(x, [lm.lm_head.weight], logits[:, :V]), [None])},
+        "gemm_skinny": {
+            "qkv_us": sweep(lambda l: K.gemm_skinny(x, [att(l).q_proj.weight, att(l).k_proj.weight, att(l).v_proj.weight],
+                                                    qkv), layers),
+            "o_us": sweep(lambda l: K.gemm_skinny(attn, [att(l).o_proj.weight], out), layers)}}
+    return table
+
+
 VARIANTS = "merged,adapters_kernels,adapters_composed"
 
 
@@ -339,7 +462,16 @@ def main():
                     help="bf16 against the weight-only MX fp8 decode (enable_fp8_decode), alternating rounds, bytes per "
                          "token, token agreement and a per-kernel table; with --lora R: merged bf16, unmerged on the "
                          "bf16 adapter GEMVs and unmerged over the e4m3 copies (enable_fp8_lora_decode)")
+    ap.add_argument("--batched", action="store_true",
+                    help="the batched-decode switch (enable_batched_decode) off against on, alternating rounds at every "
+                         "batch of --batches, and a per-launch table of the routed projections at --table-rows rows")
+    ap.add_argument("--batches", default=None, help="--batched: the batch sizes (default: 8,16,32,48,64; --batch N: 8,N)")
+    ap.add_argument("--table-rows", default="16", help="--batched: token rows of the per-launch table (a,b,...)")
     args = ap.parse_args()
+    if args.batched:
+        if args.batches is None:
+            args.batches = "8,16,32,48,64" if args.batch == 1 else (f"8,{args.batch}" if args.batch != 8 else "8")
+        return batched_main(args)
     if args.lora and args.fp8:
         return lora_fp8_main(args)
     if args.lora:
@@ -373,9 +505,7 @@ def main():
                                max(2, args.reps // 2))
             res_unc = {"ms": round(tu, 2), "tokens_equal": bool(torch.equal(toks, toks_u))}
     lm = model.language_model
-    wbytes = sum(p.numel() * p.element_size() for p in lm.model.layers.parameters())
-    wbytes += lm.lm_head.weight.numel() * lm.lm_head.weight.element_size()
-    wbytes += lm.model.norm.weight.numel() * lm.model.norm.weight.element_size()
+    wbytes = algorithmic_bytes_per_token_step(lm)
     gbs = wbytes / (per_tok * 1e-3) / 1e9
     graphs = bool(model.decode_graphs)
     print(json.dumps({
