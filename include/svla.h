@@ -745,6 +745,50 @@ int svla_action_accuracy(int64_t B, int64_t L, const int64_t* pred, int64_t ldp,
                          const int64_t* ranges, int64_t* counts, float* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sampled decoding.  The reference's predict_action calls HF generate with do_sample=False
+ * (model/modeling_spatialvla.py:491); generate(do_sample=True, temperature, top_k, top_p) is the same call's
+ * sampling form (transformers' TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, then a multinomial
+ * draw).  svla_sample_rows is that form over the softcapped bf16 logits every decode head leaves in memory.
+ * ---------------------------------------------------------------------------------------- */
+/* The settings, read from DEVICE memory by the kernel (one captured graph serves every setting and every call). */
+typedef struct svla_sample_params {
+  float temperature; /* > 0: sample; <= 0: constrained greedy (first argmax of the allowed columns, no noise) */
+  float top_p;       /* >= 1: off */
+  int32_t top_k;     /* <= 0: off */
+  int32_t nranges;   /* entries of the range table in use (<= 0: no constraint) */
+  uint64_t seed;     /* Philox key */
+  uint64_t draw;     /* advanced by the caller once per call */
+} svla_sample_params;
+/* One token per row m of bf16 logits [M][ld] (N valid columns; columns >= N are never read), any M >= 1,
+ * 1 <= N <= 2^22, ld % 8 == 0, logits 16-B aligned.  All pointers are device pointers; row_ids (int32 [M]), ranges,
+ * step and aux may be NULL.  With v_c the logit of column c:
+ *  1. allowed columns A = [lo, hi) = ranges[step[0] mod n], n = min(params->nranges, max_ranges) (int32 pairs, clamped
+ *     to [0, N); step NULL: entry 0; max_ranges: the table's capacity), or [0, N) without a table, with n <= 0 or
+ *     when the clamped range is empty.  The length in use lives in the block so that a captured launch serves
+ *     every constraint.
+ *  2. top-k (k >= 1, k < |A|): keep the allowed columns with v_c >= the k-th largest allowed value, ties at that
+ *     value all kept (TopKLogitsWarper removes scores < kth).  Exact: integer counts per distinct bf16 value.
+ *  3. top-p (< 1): with w_c = exp((v_c - vmax) / T) over the top-k set and Z their sum, t* is the largest value t with
+ *     mass{v_c >= t} >= top_p Z; keep {v_c >= t*}, ties at t* all kept (TopPLogitsWarper splits an exact tie at the
+ *     boundary by sort order; otherwise the same set).  Masses are count * round(2^40 w) in uint64 per distinct
+ *     value, w by expf, the maximum's weight exactly 1.
+ *  4. draw: token = argmax over the kept set of v_c / T + g_c, the first column on an exact tie, with
+ *     g = -log(-log u), u = ((word >> 8) + 0.5) 2^-24, word = word (c & 3) of Philox4x32-10 with key
+ *     (seed lo, seed hi) and counter (c >> 2, position, row id, draw), the low 32 bits of each; row id = row_ids[m]
+ *     or m.  Both logs are the accurate fp32 ones.  (Zero key and counter: 6627e8d5 e169c58d bc57ac4c 9b00dbd8.)
+ *  5. temperature <= 0: token = the first argmax over A, no noise and no top-k / top-p.
+ *  6. a NaN among the allowed columns: token = the first such column, both log-probabilities NaN, aux = {NaN, 0}.
+ * Outputs: token int64 [M]; logprob fp32 [M] = log(w_tok / sum of w over the kept set), the distribution sampled
+ * from (temperature <= 0: T = 1 over A); logprob_raw fp32 [M] = v_tok - logsumexp over all N columns at T = 1 (NaN
+ * when any of them is NaN); aux fp32 [M][2] = {the smallest kept value, the number of kept columns}.
+ * Deterministic: no float atomics; a row's outputs depend on its logits, its row id, position, step and params only
+ * -- not on M, the row's place or the grid (one workgroup per row; integer sums, and float sums in a fixed order). */
+int svla_sample_rows(int64_t M, int64_t N, const void* logits, int64_t ld, const svla_sample_params* params,
+                     const int32_t* row_ids, int64_t position, const int32_t* ranges, int32_t max_ranges,
+                     const int64_t* step, int64_t* token, float* logprob, float* logprob_raw, float* aux,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam / torch AdamW semantics, scripts/zero1.json:23-34).
  * ---------------------------------------------------------------------------------------- */
 /* partial sums of squares of a bf16 vector -> out[0] += sum (single fp32; deterministic tree). */

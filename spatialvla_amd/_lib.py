@@ -90,6 +90,11 @@ class Bf16Rows(ctypes.Structure):
     _fields_ = [("w", c_vp * 3), ("start", c_i64 * 4), ("ldw", c_i64), ("nseg", c_i32), ("_pad", c_i32)]
 
 
+class SampleParams(ctypes.Structure):
+    _fields_ = [("temperature", c_f32), ("top_p", c_f32), ("top_k", c_i32), ("nranges", c_i32),
+                ("seed", ctypes.c_uint64), ("draw", ctypes.c_uint64)]
+
+
 LORA_SHARED, LORA_SLICED, LORA_SUMMED = 0, 1, 2
 LORA_EPI_NONE, LORA_EPI_ROPE, LORA_EPI_GEGLU, LORA_EPI_GELU, LORA_EPI_RESID, LORA_EPI_SCALE = 0, 1, 2, 3, 4, 5
 
@@ -210,6 +215,8 @@ SIGNATURES = {
     "svla_conv2d_nhwc": (c_i32, [ctypes.POINTER(ConvArgs), c_vp]),
     "svla_action_accuracy": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_vp, c_vp,
                                      c_vp]),
+    "svla_sample_rows": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp]),
     "svla_sumsq_bf16": (c_i32, [c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "svla_adamw": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32,
                            c_vp, c_vp]),

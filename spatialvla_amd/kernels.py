@@ -977,6 +977,52 @@ def action_accuracy(pred: torch.Tensor, labels: torch.Tensor, ranges, counts=Non
     return counts, acc
 
 
+def pack_sample_params(temperature: float, top_p: float = 1.0, top_k: int = 0, seed: int = 0, draw: int = 0,
+                       nranges: int = 0) -> torch.Tensor:
+    """The 32 bytes of an svla_sample_params block (uint8 CPU tensor); copy_ it into the device block that
+    sample_rows reads.  nranges: the entries of the range table in use (0: no constraint)."""
+    sp = L.SampleParams(float(temperature), float(top_p), int(top_k), int(nranges), int(seed) & (2 ** 64 - 1),
+                        int(draw) & (2 ** 64 - 1))
+    return torch.frombuffer(bytearray(bytes(sp)), dtype=torch.uint8)
+
+
+def sample_rows(logits: torch.Tensor, N: int, params: torch.Tensor, position: int, row_ids=None, ranges=None,
+                step=None, aux: bool = False, out=None):
+    """svla_sample_rows over bf16 logits [M, >= N] (row stride a multiple of 8): params = the 32-byte device block
+    (pack_sample_params), row_ids int32 [M] or None, ranges int32 [cap, 2] device table of [lo, hi) (entry step % nranges of the block's
+    nranges <= cap entries in use; step an int64 device counter, None: entry 0) or None.  Returns (token int64 [M], logprob fp32 [M], logprob_raw fp32 [M],
+    aux fp32 [M, 2] or None); out: the first three, preallocated."""
+    _chk_bf16(logits, "sample_rows")
+    M, ld, dev = logits.shape[0], _ld(logits), logits.device
+    _req(logits.shape[1] >= N >= 1, "sample_rows: logits need N >= 1 columns")
+    _req(params.is_cuda and params.dtype == torch.uint8 and params.is_contiguous() and params.numel() >= 32
+         and params.data_ptr() % 8 == 0, "sample_rows: params must be the 32-byte uint8 device block")
+    if row_ids is not None:
+        _req(row_ids.is_cuda and row_ids.dtype == torch.int32 and row_ids.is_contiguous() and row_ids.numel() >= M,
+             "sample_rows: row_ids must be a contiguous int32 device vector [M]")
+    nr = 0
+    if ranges is not None:
+        _req(ranges.is_cuda and ranges.dtype == torch.int32 and ranges.is_contiguous() and ranges.dim() == 2
+             and ranges.shape[1] == 2 and ranges.shape[0] >= 1, "sample_rows: ranges must be int32 [n, 2] on the device")
+        nr = ranges.shape[0]
+        if step is not None:
+            _req(step.is_cuda and step.dtype == torch.int64 and step.numel() >= 1,
+                 "sample_rows: step must be an int64 device scalar")
+    else:
+        step = None
+    if out is None:
+        out = (torch.empty(M, dtype=torch.int64, device=dev), torch.empty(M, dtype=torch.float32, device=dev),
+               torch.empty(M, dtype=torch.float32, device=dev))
+    tok, lp, lpr = out
+    _req(tok.dtype == torch.int64 and lp.dtype == lpr.dtype == torch.float32
+         and all(t.is_cuda and t.is_contiguous() and t.numel() >= M for t in out), "sample_rows: out tensors")
+    ax = torch.empty(M, 2, dtype=torch.float32, device=dev) if aux else None
+    L.check(L.lib().svla_sample_rows(M, int(N), logits.data_ptr(), ld, params.data_ptr(), _ptr(row_ids), int(position),
+                                     _ptr(ranges), nr, _ptr(step), tok.data_ptr(), lp.data_ptr(), lpr.data_ptr(),
+                                     _ptr(ax), _stream()), "svla_sample_rows")
+    return tok, lp, lpr, ax
+
+
 def sumsq(x_flat, out, n_partial=4096):
     part = torch.empty(n_partial, dtype=torch.float32, device=x_flat.device)
     L.check(L.lib().svla_sumsq_bf16(x_flat.numel(), x_flat.data_ptr(), part.data_ptr(), n_partial, out.data_ptr(),

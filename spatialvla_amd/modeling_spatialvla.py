@@ -708,6 +708,80 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         self.language_model.enable_batched_decode(enabled)
         self.clear_decode_cache()
 
+    SAMPLE_MAX_RANGES = 16     # capacity of a decode state's allowed-range table (allowed_ranges entries)
+
+    @property
+    def sampled_decode(self) -> bool:
+        return bool(self.__dict__.get("_svla_sampled_decode", False))
+
+    def enable_sampled_decode(self, on: bool = True):
+        """Sampled decoding with log-probabilities (opt-in, default off): predict_action takes do_sample, temperature,
+        top_k, top_p, seed, allowed_ranges and return_logprobs, and generate(do_sample=True) runs.  While on, every
+        decode head is followed by svla_sample_rows (include/svla.h: allowed column range, top-k, top-p, Gumbel-max
+        over Philox4x32-10, the token's log-probability under the sampled distribution and under the raw softmax),
+        inside the captured prefill and step graphs; the settings live in a device block the host writes before the
+        first replay, so one graph per cache position serves every setting and every call.  A row's noise is keyed by
+        (seed, draw, cache position, sequence index): independent of the batch size and of the other rows.  Without
+        do_sample the kernel runs its greedy form and the tokens are those of the switch-off path.  Works under
+        enable_fp8_decode, enable_lora_decode (both forms), enable_fp8_lora_decode and enable_batched_decode: it only
+        reads the logits they write.  Toggling drops the captured decode states."""
+        self.__dict__["_svla_sampled_decode"] = bool(on)
+        self.clear_decode_cache()
+
+    def _sample_args(self, what, do_sample, temperature, top_k, top_p, seed, allowed_ranges, return_logprobs=False):
+        """Validate a call's sampling arguments; returns None for a plain greedy call with the switch off, else the
+        settings dict of _write_sample_params."""
+        asked = (bool(do_sample) or return_logprobs or allowed_ranges is not None or seed is not None
+                 or float(temperature) != 1.0 or int(top_k) != 0 or float(top_p) != 1.0)
+        if not self.sampled_decode:
+            if asked:
+                raise RuntimeError(f"{what}: sampling arguments need enable_sampled_decode() (off by default)")
+            return None
+        if do_sample and not float(temperature) > 0:
+            raise ValueError(f"{what}: `temperature` (={temperature}) has to be a strictly positive float with "
+                             "do_sample=True; use do_sample=False for greedy decoding")
+        if do_sample and not (int(top_k) >= 0 and float(top_p) > 0):
+            raise ValueError(f"{what}: top_k must be >= 0 and top_p > 0")
+        ranges = []
+        if allowed_ranges is not None:
+            ranges = [(int(lo), int(hi)) for lo, hi in allowed_ranges]
+            V = self.language_model.lm_head.weight.shape[0]
+            if not 1 <= len(ranges) <= self.SAMPLE_MAX_RANGES or any(not 0 <= lo < hi <= V for lo, hi in ranges):
+                raise ValueError(f"{what}: allowed_ranges must be 1..{self.SAMPLE_MAX_RANGES} pairs 0 <= lo < hi <= {V}")
+        if do_sample and seed is None:
+            # a fresh seed per call from torch's default generator: torch.manual_seed makes a run of calls reproducible
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        # the kernel's draw counter stays 0 here: a call is determined by its seed alone (a counter kept by the model
+        # would make a re-seeded run depend on the calls before it)
+        return {"temperature": float(temperature) if do_sample else 0.0, "top_k": int(top_k) if do_sample else 0,
+                "top_p": float(top_p) if do_sample else 1.0, "seed": int(seed or 0), "draw": 0, "ranges": ranges}
+
+    @staticmethod
+    def _sample_buffers(B, cap, dev, max_ranges):
+        """The sampler's share of a decode state: the parameter block, the row ids (sequence index), the range table
+        with the generated-token counter, the kernel's outputs and the log-probabilities at each cache position."""
+        return {"params": torch.zeros(32, dtype=torch.uint8, device=dev),
+                "rows": torch.arange(B, dtype=torch.int32, device=dev),
+                "ranges": torch.zeros(max_ranges, 2, dtype=torch.int32, device=dev),
+                "step": torch.zeros(1, dtype=torch.int64, device=dev),
+                "lps": torch.zeros(2, B, cap + 1, dtype=torch.float32, device=dev)}
+
+    @staticmethod
+    def _write_sample_params(sb, sa):
+        """Host -> device: the settings of one call (before the first graph replay) and the token counter's reset."""
+        sa = sa or {"temperature": 0.0, "top_k": 0, "top_p": 1.0, "seed": 0, "draw": 0, "ranges": []}
+        sb["params"].copy_(K.pack_sample_params(sa["temperature"], sa["top_p"], sa["top_k"], sa["seed"], sa["draw"],
+                                                len(sa["ranges"])))
+        if sa["ranges"]:
+            sb["ranges"][:len(sa["ranges"])].copy_(torch.tensor(sa["ranges"], dtype=torch.int32))
+        sb["step"].zero_()
+
+    @staticmethod
+    def _sample(sb, logits2d, position):
+        """svla_sample_rows over a head's logits [B, V] -> (token [B], logprob [B], logprob_raw [B])."""
+        return K.sample_rows(logits2d, logits2d.shape[1], sb["params"], position, sb["rows"], sb["ranges"],
+                             sb["step"])[:3]
+
     def _refuse_lora_under_fp8_decode(self, what: str):
         if self.fp8_decode:
             raise RuntimeError(f"{what}: weight-only fp8 decode is on (enable_fp8_decode): call "
@@ -1283,6 +1357,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 self._fp8_decode_key(), self._fp8_lora_decode_key())
         if self.batched_decode:  # ... and the batched-decode switch selects other kernels: a sixth element while on
             wptr += ("batched",)
+        if self.sampled_decode:  # ... and the sampler follows every head: graphs with and without it are never mixed
+            wptr += ("sampled",)
         if st is not None and st["wptr"] != wptr:  # weights were rebound since capture: the graphs are stale
             states.pop(key)
             st = None
@@ -1301,6 +1377,8 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                   "cls": KVMask(torch.ones(B, 1, dtype=torch.uint8, device=dev)),
                   "pool": torch.cuda.graph_pool_handle() if dev.type == "cuda" else None,
                   "side": torch.cuda.Stream(device=dev) if dev.type == "cuda" else None}
+            if self.sampled_decode:
+                st["sample"] = self._sample_buffers(B, cap, dev, self.SAMPLE_MAX_RANGES)
             states[key] = st
         states.move_to_end(key)
         return st
@@ -1319,7 +1397,9 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         h, _ = self.language_model.model(hidden, KVMask(x["cls"]), pos, cache=cache)
         stash = {}
         tgt = torch.full((ids.shape[0],), -1, dtype=torch.int64, device=ids.device)
-        self.language_model.head(h[:, -1:].contiguous(), tgt, stash)
+        logits, _ = self.language_model.head(h[:, -1:].contiguous(), tgt, stash)
+        if "sample" in st:  # the first token, stored at cache position P
+            return self._sample(st["sample"], logits, ids.shape[1])
         return stash["argmax"]
 
     def _prefill_graph(self, st, x):
@@ -1370,13 +1450,22 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         h, _ = self.language_model.model(self._merge_inputs(tok, None), st["cls"], pos, cache=cache)
         stash = {}
         tgt = torch.full((tok.shape[0],), -1, dtype=torch.int64, device=tok.device)
-        self.language_model.head(h[:, -1:].contiguous(), tgt, stash, decode=True)
+        logits, _ = self.language_model.head(h[:, -1:].contiguous(), tgt, stash, decode=True)
+        if "sample" in st:  # the token stored at cache position p0 + 1
+            return self._sample(st["sample"], logits, p0 + 1)
         return stash["argmax"]
 
     def _greedy_bookkeep(self, st, p0, am):
         """The greedy loop's per-token update on the device (so a run of steps needs no host round trip): rows that
         already emitted eos get pad, newly finished rows are marked, the token is fed to the next step and kept at
-        its cache position p0 + 1 (reference generate: unfinished_sequences / pad_token_id handling)."""
+        its cache position p0 + 1 (reference generate: unfinished_sequences / pad_token_id handling).  With the
+        sampler on, `am` is its (token, logprob, logprob_raw): the log-probabilities are kept at the same position
+        (0 for the pads of finished rows) and the generated-token counter advances."""
+        if "sample" in st:
+            am, lp, lpr = am
+            sb = st["sample"]
+            sb["lps"][:, :, p0 + 1].copy_(torch.where(st["fin"].view(1, -1), 0.0, torch.stack((lp, lpr))))
+            sb["step"].add_(1)
         nxt = torch.where(st["fin"], st["pad"], am.view(-1, 1))
         st["fin"].logical_or_(nxt == st["eos"])
         st["tok"].copy_(nxt)
@@ -1393,9 +1482,12 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # eager warm-up (lazy kernel attributes); rewrites row p0 identically
                 saved = (st["tok"].clone(), st["fin"].clone())
+                step = st["sample"]["step"].clone() if "sample" in st else None
                 self._greedy_bookkeep(st, p0, self._decode_body(st, p0))
                 st["tok"].copy_(saved[0])
                 st["fin"].copy_(saved[1])
+                if step is not None:
+                    st["sample"]["step"].copy_(step)
             cache.seen_tokens = p0
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
@@ -1409,16 +1501,31 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         return g[1]
 
     @torch.no_grad()
-    def predict_action(self, model_inputs, max_new_tokens: int = 256, eos_token_id: Optional[int] = None):
+    def predict_action(self, model_inputs, max_new_tokens: int = 256, eos_token_id: Optional[int] = None,
+                       do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                       seed: Optional[int] = None, allowed_ranges=None, return_logprobs: bool = False):
         """Greedy decode with a KV cache (reference :484-492 -> generate(max_new_tokens=256, do_sample=False)
         with HybridCache).  Prefill: the prompt (image features merged, positions 1..P) attends bidirectionally
         (:294) and fills the cache; decode: one token per step at position P+i+1 (:473-474), no pixel values
         after step 0 (:475-476), attending to the prompt and every earlier generated token.  Stops when every
-        sequence has emitted eos or after max_new_tokens."""
+        sequence has emitted eos or after max_new_tokens.
+
+        With enable_sampled_decode() (the arguments below raise without it): do_sample draws every token by
+        svla_sample_rows under temperature / top_k (0 = off) / top_p (1 = off), HF generate's warpers; seed: an
+        explicit seed makes the call reproducible on its own, None takes a fresh one per call from torch's default
+        generator (so torch.manual_seed makes a run of calls reproducible).  allowed_ranges: (lo, hi) token-id pairs
+        applied cyclically to the generated-token index (SpatialVLAProcessor.action_token_ranges(): translation,
+        rotation, gripper), also for greedy calls; eos is then never allowed, so the loop runs max_new_tokens steps --
+        pass three times the number of actions.  return_logprobs: the result is (tokens, logprobs [B, n] fp32 under the
+        distribution sampled from, logprobs_raw [B, n] fp32 under the unconstrained softmax at temperature 1)."""
         self._require_merged("predict_action")
         self._wait_all_params()
+        sa = self._sample_args("predict_action", do_sample, temperature, top_k, top_p, seed, allowed_ranges,
+                               return_logprobs)
         ids, pv, intr, am, dev = self._predict_inputs(model_inputs)
         eos = eos_token_id if eos_token_id is not None else self.config.text_config.eos_token_id
+        if sa is not None and sa["ranges"]:
+            eos = None
         B, P = ids.shape
         graphs = self.decode_graphs and dev.type == "cuda"
         st = self._decode_state(B, P + max_new_tokens, dev)
@@ -1438,7 +1545,14 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         # the frozen Zoe forward is captured with the rest of the prefill: every convolution of it runs on libsvla
         # (zoe_fast), no vendor library creates handles lazily under the capture
         prefill = {"ids": ids, "pv": pv, "intr": intr, "cls": cls, "kinv": kinv}
+        sb = st.get("sample")
+        if sb is not None:
+            self._write_sample_params(sb, sa)
         first = self._prefill_graph(st, prefill) if graphs else self._prefill_body(st, prefill)
+        if sb is not None:
+            first, lp, lpr = first
+            sb["lps"][:, :, P].copy_(torch.stack((lp, lpr)))
+            sb["step"].fill_(1)
         cache.seen_tokens = P
         # the per-token update runs on the device (_greedy_bookkeep); the host reads the finished flags only every
         # EOS_CHECK_EVERY steps and cuts the output where the last row finished -- the tokens and the length are the
@@ -1468,6 +1582,9 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 n = toks.shape[1]
                 first_eos = torch.where(hit, torch.arange(n, device=dev), n).min(1).values
                 toks = toks[:, :int(first_eos.max()) + 1]
+        if return_logprobs:
+            lps = sb["lps"][:, :, P:P + toks.shape[1]].clone()
+            return toks, lps[0], lps[1]
         return toks
 
     # ------------------------------------------------------------------ HF generate() surface
@@ -1493,11 +1610,15 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
     @torch.no_grad()
     def generate(self, input_ids=None, pixel_values=None, intrinsic=None, attention_mask=None,
                  max_new_tokens: Optional[int] = None, do_sample: Optional[bool] = None, eos_token_id=None,
-                 pad_token_id=None, generation_config=None, **kwargs):
+                 pad_token_id=None, generation_config=None, temperature: Optional[float] = None,
+                 top_k: Optional[int] = None, top_p: Optional[float] = None, seed: Optional[int] = None, **kwargs):
         """Greedy `generate` as the reference's predict_action calls it (:491, HF generate with do_sample=False over a
         HybridCache): the loop runs prepare_inputs_for_generation -> forward(past_key_values=Gemma2KVCache) per step
         and returns prompt + new tokens; finished sequences get pad_token_id, the loop stops once every sequence
-        emitted eos.  Every step is eager here; predict_action is the graph-replayed fast path with the same tokens."""
+        emitted eos.  Every step is eager here; predict_action is the graph-replayed fast path with the same tokens.
+        do_sample=True needs enable_sampled_decode(): every step's token is then drawn by svla_sample_rows under
+        temperature / top_k / top_p (HF's defaults: 1.0 / 50 / 1.0, or the generation_config's), keyed by `seed` (None:
+        one from torch's default generator) and the token's position."""
         # HF precedence: explicit arguments override the generation_config, which overrides the defaults
         if generation_config is not None:
             if max_new_tokens is None:
@@ -1506,10 +1627,20 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
                 do_sample = getattr(generation_config, "do_sample", None)
             eos_token_id = getattr(generation_config, "eos_token_id", None) if eos_token_id is None else eos_token_id
             pad_token_id = getattr(generation_config, "pad_token_id", None) if pad_token_id is None else pad_token_id
+            temperature = getattr(generation_config, "temperature", None) if temperature is None else temperature
+            top_k = getattr(generation_config, "top_k", None) if top_k is None else top_k
+            top_p = getattr(generation_config, "top_p", None) if top_p is None else top_p
         max_new_tokens = 256 if max_new_tokens is None else int(max_new_tokens)
         do_sample = bool(do_sample)
-        if do_sample or int(kwargs.pop("num_beams", 1)) != 1:
-            raise NotImplementedError("generate: greedy decoding only (the reference calls do_sample=False)")
+        if int(kwargs.pop("num_beams", 1)) != 1:
+            raise NotImplementedError("generate: greedy decoding and sampling only (no beam search)")
+        if do_sample and not self.sampled_decode:
+            raise NotImplementedError("generate: greedy decoding only (the reference calls do_sample=False); "
+                                      "do_sample=True needs enable_sampled_decode()")
+        sa = None
+        if do_sample:  # HF's defaults: temperature 1.0, top_k 50, top_p 1.0
+            sa = self._sample_args("generate", True, 1.0 if temperature is None else temperature,
+                                   50 if top_k is None else top_k, 1.0 if top_p is None else top_p, seed, None)
         kwargs.pop("token_type_ids", None)
         for k in ("output_attentions", "output_hidden_states", "return_dict_in_generate", "use_cache"):
             kwargs.pop(k, None)
@@ -1531,12 +1662,18 @@ class SpatialVLAForConditionalGeneration(SpatialVLAPreTrainedModel, GenerationMi
         cache = self.new_cache(B, P + max_new_tokens)
         cache_position = torch.arange(P, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        if sa is not None:
+            sb = self._sample_buffers(B, 0, dev, 1)
+            self._write_sample_params(sb, sa)
         for _ in range(max_new_tokens):
             mi = self.prepare_inputs_for_generation(ids, past_key_values=cache, cache_position=cache_position,
                                                     pixel_values=pv, intrinsic=intr, attention_mask=am)
             mi.pop("cache_position")
-            self(**mi, return_dict=True)
-            nxt = self.action_argmax().view(B, -1)[:, -1]
+            out = self(**mi, return_dict=True)
+            if sa is not None:  # the step's last-position logits [B, V] (row stride: the padded vocabulary)
+                nxt = self._sample(sb, out.logits[:, -1], ids.shape[1])[0]
+            else:
+                nxt = self.action_argmax().view(B, -1)[:, -1]
             if eos is not None:
                 nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
                 finished = finished | (nxt == eos)

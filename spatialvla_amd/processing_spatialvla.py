@@ -189,6 +189,14 @@ class SpatialVLAProcessor(ProcessorMixin):
         names = self.tokenizer.model_input_names + self.image_processor.model_input_names
         return list(dict.fromkeys(names))
 
+    def action_token_ranges(self):
+        """[(lo, hi)] half-open token-id ranges of the translation, rotation and gripper tokens, in the order generated
+        token i mod 3 takes them: the `allowed_ranges` of predict_action's sampled decode (decode_actions clips any
+        other id into these ranges; a constrained sampler never emits one)."""
+        at = self.action_tokenizer
+        return [(int(t.token_start_idx), int(t.token_end_idx) + 1)
+                for t in (at.translation_tokenizer, at.rotation_tokenizer, at.gripper_tokenizer)]
+
     def decode_actions(self, generation_outputs: torch.Tensor, unnorm_key: Optional[str] = None
                        ) -> Dict[str, np.ndarray]:
         """Reference :216-254: the first 3 x action_chunk_size generated ids -> {"actions" (chunk, 7) in dataset

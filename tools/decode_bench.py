@@ -439,6 +439,103 @@ def _batched_table(args, K, lm, M, dev):
     return table
 
 
+def sample_main(args):
+    """--sample (with --batched and / or --fp8 applied to both models): ms per decode step of greedy decoding with
+    enable_sampled_decode off, and with it on for the greedy form and three sampling settings -- the full vocabulary
+    (temperature 1, no filter), top_k 50 / top_p 0.95 at temperature 0.7, and temperature 1 inside the action-token
+    ranges -- in one process, graph replay, alternating rounds, at every batch of --batches (default 1,16).  The
+    settings live in the device block, so the four switch-on legs replay the same graphs.  Also svla_sample_rows
+    alone at the model's vocabulary for M = 1, 16, 64 rows: device time per launch inside one captured graph."""
+    from bench import build_model, make_batch
+    from spatialvla_amd import kernels as K, presets
+    dev = torch.device("cuda:0")
+    cfgd = json.loads(json.dumps(presets.spatialvla_4b()))
+    n_long = args.new_tokens + args.long
+    n_long += (-n_long) % 3  # whole actions under the range constraint
+    models = {"off": build_model(cfgd, dev).eval(), "on": build_model(cfgd, dev).eval()}
+    models["on"].enable_sampled_decode()
+    for m in models.values():
+        if args.batched:
+            m.enable_batched_decode()
+        if args.fp8:
+            m.enable_fp8_decode()
+        m.predict_depth = lambda pv, _f=m.predict_depth: torch.cat([_f(pv[i:i + 8]) for i in range(0, pv.shape[0], 8)], 0)
+    r = models["on"].action_token_ranges()
+    ranges = [(r[0], r[1] + 1), (r[2], r[3] + 1), (r[4], r[5] + 1)]
+    legs = {"off_greedy": ("off", {}), "on_greedy": ("on", {}),
+            "on_full_vocab_T1": ("on", dict(do_sample=True, seed=1)),
+            "on_T0.7_k50_p0.95": ("on", dict(do_sample=True, temperature=0.7, top_k=50, top_p=0.95, seed=1)),
+            "on_action_ranges_T1": ("on", dict(do_sample=True, seed=1, allowed_ranges=ranges))}
+    results = []
+    for batch in [int(v) for v in (args.batches or "1,16").split(",")]:
+        b = make_batch(cfgd, batch, 4321, dev)
+        P = int((b["token_type_ids"][0] == 0).sum())
+        inputs = {"input_ids": b["input_ids"][:, :P], "pixel_values": b["pixel_values"], "intrinsic": b["intrinsic"]}
+        run = lambda leg, n: models[legs[leg][0]].predict_action(  # noqa: E731
+            inputs, max_new_tokens=n, eos_token_id=-1, **legs[leg][1])
+        toks, rounds = {}, []
+        with torch.no_grad():
+            for leg in legs:  # warm-up: every graph the rounds replay is captured here
+                run(leg, 1)
+                toks[leg] = run(leg, n_long)
+            for _ in range(args.rounds):
+                row = {}
+                for leg in legs:
+                    t1, _ = timed(lambda: run(leg, 1), args.reps)
+                    tl, _ = timed(lambda: run(leg, n_long), args.reps)
+                    row[leg] = round((tl - t1) / (n_long - 1), 4)
+                rounds.append(row)
+        per = {n: [r_[n] for r_ in rounds] for n in legs}
+        med = {n: sorted(v)[len(v) // 2] for n, v in per.items()}
+        res = {"batch": batch, "prompt_tokens": P, "decode_steps_timed": n_long - 1, "rounds_ms_per_step": rounds,
+               "ms_per_step_median": med, "ms_per_step_min_max": {n: [min(v), max(v)] for n, v in per.items()},
+               "spread_ms": round(max(max(v) - min(v) for v in per.values()), 4),
+               "minus_off_greedy_ms": {n: round(med[n] - med["off_greedy"], 4) for n in legs if n != "off_greedy"},
+               "on_greedy_tokens_equal_off": bool(torch.equal(toks["on_greedy"], toks["off_greedy"]))}
+        results.append(res)
+        for m in models.values():
+            m.clear_decode_cache()
+        print(json.dumps(res), file=sys.stderr, flush=True)
+
+    # the kernel alone: 20 launches over the same logits in one captured graph, device time per launch
+    V = models["on"].language_model.lm_head.weight.shape[0]
+    ld = K.round_up(V, 64)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    rtab = torch.tensor(ranges, dtype=torch.int32, device=dev)
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    kernel = {}
+    for M in (1, 16, 64):
+        x = torch.randn(M, ld, generator=g) * 4.0
+        logits = (30.0 * torch.tanh(x / 30.0)).to(torch.bfloat16).to(dev)
+        out = (torch.empty(M, dtype=torch.int64, device=dev), torch.empty(M, dtype=torch.float32, device=dev),
+               torch.empty(M, dtype=torch.float32, device=dev))
+        row = {}
+        for name, (T, k, p, nr) in {"greedy": (0.0, 0, 1.0, 0), "full_vocab_T1": (1.0, 0, 1.0, 0),
+                                    "T1_p0.9": (1.0, 0, 0.9, 0), "T0.7_k50_p0.95": (0.7, 50, 0.95, 0),
+                                    "action_ranges_T1": (1.0, 0, 1.0, 3)}.items():
+            params = K.pack_sample_params(T, p, k, 1, 0, nr).to(dev)
+
+            def launches():
+                for i in range(20):
+                    K.sample_rows(logits, V, params, 300 + i, None, rtab, step, out=out)
+            launches()
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                launches()
+            gr.replay()
+            t, _ = timed(gr.replay, max(5, args.reps))
+            row[name] = round(t * 1e3 / 20, 2)
+        kernel[str(M)] = row
+    print(json.dumps({
+        "metric": "SpatialVLA-4B decode, greedy against sampled (enable_sampled_decode)", "unit": "ms per decode step",
+        "batched_decode": bool(args.batched), "fp8_decode": bool(args.fp8), "batches": results,
+        "sample_rows_us_per_launch_by_rows": kernel, "vocabulary": V,
+        "kernel_note": "device time per launch, 20 launches over the same (cache-resident) logits in one captured graph",
+        "decode_graphs": bool(models["off"].decode_graphs), "dtype": "bf16",
+        "data": "synthetic OXE-shaped prompt, random-init weights"}), flush=True)
+
+
 VARIANTS = "merged,adapters_kernels,adapters_composed"
 
 
@@ -467,7 +564,12 @@ def main():
                          "batch of --batches, and a per-launch table of the routed projections at --table-rows rows")
     ap.add_argument("--batches", default=None, help="--batched: the batch sizes (default: 8,16,32,48,64; --batch N: 8,N)")
     ap.add_argument("--table-rows", default="16", help="--batched: token rows of the per-launch table (a,b,...)")
+    ap.add_argument("--sample", action="store_true",
+                    help="greedy against sampled decode (enable_sampled_decode) at every batch of --batches (default "
+                         "1,16), alternating rounds, and svla_sample_rows alone; --batched / --fp8 apply to both models")
     args = ap.parse_args()
+    if args.sample:
+        return sample_main(args)
     if args.batched:
         if args.batches is None:
             args.batches = "8,16,32,48,64" if args.batch == 1 else (f"8,{args.batch}" if args.batch != 8 else "8")
