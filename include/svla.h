@@ -458,6 +458,11 @@ int svla_gemm_skinny(int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx
  *   0 = visible to every query, 1 = visible to queries i >= j, 2 = never visible;
  * plus an optional sliding window (key j masked for query i when i - j >= window, 0 = off).
  * Masked scores take the bf16 minimum (-3.3895e38) exactly as the reference's additive mask.
+ * A query row with no visible key (left padding: its own key is class 2 and no class-0 key is in reach) is uniform
+ * over all L keys, with and without softcap, in svla_attn_fwd (out = mean of V) and in both backwards (p = 1/L on
+ * every key, and the gradient reaches the masked scores as through the additive mask).  The lse of such a row is
+ * ln(L) - 120 ln 2 with softcap and (bf16 minimum) without, where ln(L) is below fp32 resolution: the backwards
+ * recognise the row by it, so pass the forward's lse on unchanged.
  * q/k/v are read in place from projection outputs: element (b, t, h, d) at
  *   base + (b*L + t)*ld + h*D + d.
  * q and k arrive already rotated (Gemma2 RoPE is applied in the QKV GEMM epilogue, SVLA_EPI_ROPE).

@@ -216,7 +216,8 @@ constexpr int tile_bytes(int rows) { return rows * Cfg<D>::RS * 2; }
 //   p = 2^(C0 + C1*r),  c2 = 2*scale*log2(e)/cap,  C0 = cap*log2(e),  C1 = -2*cap*log2(e)
 // -- two v_exp_f32 and one v_rcp_f32 per score.  A masked key gets p = 2^-120 instead of 0: at least one visible
 // key contributes >= e^-cap = 2e-22, so masked keys weigh < 1e-14 of a row, and a row with no visible key
-// becomes uniform over all keys, as the reference's softmax over equal finfo.min logits does.
+// becomes uniform over all keys, as the reference's softmax over equal finfo.min logits does (forward and backward:
+// the backward's p = 2^(-120 - lse2) is 1/L there; without a softcap see dead_row).
 struct CapExp {
   float c2, C0, C1;
   __device__ __forceinline__ CapExp(float scale, float cap) {
@@ -537,16 +538,22 @@ __device__ __forceinline__ void rope_t_acc(f32x4 (&acc)[NDT], const svla_attn_ar
 // Per-score backward factor z = dS * dt/ds * scale (the softcap chain rule), for the score s (raw dot product)
 // of a query with log2-domain lse2 and delta, or 0 when out of range.  Same p as the forward (CapExp, masked keys
 // at 2^-120 of the row scale).
+// A row with no visible key (no softcap): the forward's lse (MASKVAL + log2(L)) / LOG2E loses log2(L) in fp32, so
+// exp2(MASKVAL - lse2) is 1 (or, one ulp off, 0 or inf) where the row's p is 1/L.  Such a row is recognised by its
+// lse (no visible key can score below MASKVAL / 2) and every live key of it gets p = inv_l = 1/L, as the forward.
+__device__ __forceinline__ bool dead_row(float lse2) { return lse2 <= 0.5f * MASKVAL; }
+
 template <bool CAP>
 __device__ __forceinline__ float score_grad(float s, float dp, float lse2, float delta, bool masked, const CapExp& ce,
-                                            float scale) {
+                                            float scale, float inv_l) {
   const float LOG2E = 1.4426950408889634f;
   if constexpr (CAP) {
     const float r = ce.r(s);
     const float p = __builtin_amdgcn_exp2f((masked ? MASKED_LG2P : ce.lg2p(r)) - lse2);
     return p * (dp - delta) * (4.f * r * (1.f - r)) * scale;  // d tanh = 1 - (1 - 2r)^2
   } else {
-    const float p = __builtin_amdgcn_exp2f((masked ? MASKVAL : s * (scale * LOG2E)) - lse2);
+    float p = __builtin_amdgcn_exp2f((masked ? MASKVAL : s * (scale * LOG2E)) - lse2);
+    if (masked && dead_row(lse2)) p = inv_l;
     return p * (dp - delta) * scale;
   }
 }
@@ -616,6 +623,7 @@ __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_bwd_dkv_kernel(svl
 #pragma unroll
   for (int i = 0; i < NDT; ++i) adk[i] = adv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const CapExp ce(a.scale, CAP ? a.softcap : 1.f);
+  const float inv_l = 1.f / (float)L;
 
   issue_q(0, ldsQ2);
   for (int step = 0; step < nsteps; ++step) {
@@ -676,6 +684,7 @@ __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_bwd_dkv_kernel(svl
             z = p * (dp[mt][j] - d4[j]) * (4.f * r * (1.f - r)) * a.scale;
           } else {
             p = __builtin_amdgcn_exp2f((masked ? MASKVAL : s[mt][j] * (a.scale * LOG2E)) - l4[j]);
+            if (masked && dead_row(l4[j])) p = inv_l;  // fully masked row: uniform over the L keys
             z = p * (dp[mt][j] - d4[j]) * a.scale;
           }
           pv[4 * mt + j] = live ? p : 0.f;
@@ -757,7 +766,8 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(int B, int L, int H, co
 // Padded query columns: when L % 64 is 1..32 the dK/dV kernel writes dS^T only up to query round32(L), so columns
 // round32(L)..round64(L)-1 of the workspace hold whatever the allocator left there (possibly NaN patterns).  Query
 // column q of dS^T feeds only output row q of dQ (it is the A operand's row), and rows q >= L are never stored (the
-// q < L test of the epilogue), so those columns cannot reach a result; no zero-fill is needed.
+// q < L test of the epilogue), so those columns cannot reach a result; no zero-fill is needed
+// (tests/test_attention_masks_gpu.py::test_stored_ds_workspace_poisoned runs it on a workspace of NaN patterns).
 // LDS row pitch of the dS^T tile (bf16): the A-operand reads take keys 4g + j (g = lane >> 4) of 16 queries, i.e.
 // rows 4 apart; at a 64-element (128-B) pitch those four rows share one 8-bank span (4-way conflicts, 21.7 % of the
 // kernel's LDS cycles, profiles/r5b_block_pmc.txt); at 72 (144 B) rows 4g start 16g banks apart: conflict-free,
@@ -893,6 +903,7 @@ __global__ __launch_bounds__(256 * NH, 1) void attn_bwd_dq_kernel(svla_attn_args
 #pragma unroll
   for (int i = 0; i < NDT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const CapExp ce(a.scale, CAP ? a.softcap : 1.f);
+  const float inv_l = 1.f / (float)L;
   for (int kt = 0; kt < nkt; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -926,7 +937,7 @@ __global__ __launch_bounds__(256 * NH, 1) void attn_bwd_dq_kernel(svla_attn_args
           live = live && kj < L;
           masked = !visible(lcls[kj < L ? kj : 0], kj, qi, a.sliding_window);
         }
-        const float z = score_grad<CAP>(s[nt][j], dp[nt][j], lq, dq_, masked, ce, a.scale);
+        const float z = score_grad<CAP>(s[nt][j], dp[nt][j], lq, dq_, masked, ce, a.scale, inv_l);
         zz[nt][j] = live ? z : 0.f;
       }
 #pragma unroll

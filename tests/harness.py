@@ -149,16 +149,32 @@ def greedy_tokens_agree(got: torch.Tensor, ref: torch.Tensor, margins: torch.Ten
     return n_cmp, n_ok
 
 
-def tiny_parity_run(device="cuda:0", batch=2, seed=7, ragged=False):
+def apply_overrides(cfgd, overrides):
+    """Nested update of a config dict in place: {"text_config": {"sliding_window": 16}} changes that one key."""
+    for k, v in (overrides or {}).items():
+        if isinstance(v, dict) and isinstance(cfgd.get(k), dict):
+            apply_overrides(cfgd[k], v)
+        else:
+            cfgd[k] = v
+    return cfgd
+
+
+def tiny_parity_run(device="cuda:0", batch=2, seed=7, ragged=False, overrides=None, depth=None):
     """End-to-end tiny-config parity: HIP model on `device` vs CPU oracle, same weights and batch.
     The oracle's depth map is fed to both sides so the frozen 3p depth estimator's GPU/CPU numerics
-    do not mask hot-path differences (depth parity is tested separately)."""
+    do not mask hot-path differences (depth parity is tested separately).
+    overrides: nested config changes applied to both sides (apply_overrides).  depth: a [B, 1, H, W] depth map fed
+    to both sides instead of the oracle estimator's."""
     from spatialvla_amd import presets
-    cfgd = cfg_dict("tiny")
+    cfgd = apply_overrides(cfg_dict("tiny"), overrides)
     b = presets.synthetic_batch(cfgd, batch=batch, seed=seed, ragged=ragged)
     bc = batch_tensors(b, "cpu")
-    P, zoe = build_oracle(cfgd)
-    loss_r, logits_r, grads_r, cap = run_oracle(P, zoe, cfgd, bc)
+    if depth is None:
+        P, zoe = build_oracle(cfgd)
+    else:
+        import spatialvla_oracle as O
+        P, zoe = O.build_params(cfgd, SEED), None
+    loss_r, logits_r, grads_r, cap = run_oracle(P, zoe, cfgd, bc, depth=depth)
     model = build_hip_model(cfgd, device)
     bd = {k: v.to(device) for k, v in bc.items()}
     loss_h, logits_h, grads_h, am = run_hip(model, bd, depth=cap["depth"])

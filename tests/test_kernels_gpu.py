@@ -706,7 +706,9 @@ def _ref_attn(q, k, v, scale, cap, kv_class, window, cos=None, sin=None):
         vis = torch.ones(1, 1, L, L, dtype=torch.bool, device=q.device)
     if window:
         vis = vis & ((i - j) < window)
-    s_ = torch.where(vis, s_, torch.tensor(-3.3895313892515355e38, device=q.device))
+    # masked scores take finfo(bf16).min and keep their gradient, as through the reference's additive mask (fp32
+    # s + min rounds to min): a torch.where on the constant would block the gradient of fully masked rows
+    s_ = torch.where(vis, s_, s_ - s_.detach() + (-3.3895313892515355e38))
     p = torch.softmax(s_, -1)
     return (p @ v).transpose(1, 2)
 
