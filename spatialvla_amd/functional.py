@@ -726,84 +726,78 @@ LORA_DECODE_KERNELS = [os.environ.get("SVLA_LORA_DECODE_KERNELS", "1") != "0"]
 LORA_DECODE_EMB_HEAD_KERNELS = [os.environ.get("SVLA_LORA_DECODE_EMB_HEAD_KERNELS", "1") != "0"]
 
 
-def _lora_decode_ok(x_rows, k, weights, norm=False) -> bool:
-    return (LORA_DECODE_KERNELS[0] and all(w.stride(1) == 1 for w in weights)
-            and K.lora_gemv_ok(x_rows, k, [w.shape[0] for w in weights], norm))
+def decode_proj_ok(form: str, M: int, k: int, weights, norm: bool = False, geglu: bool = False) -> bool:
+    """Whether a decode step's projection of M rows over `weights` [N_i, k] runs on the kernel of `form` (decode_proj's
+    rules 2 and 4; False: the next rule down).  norm: the norm pair runs in the prologue; geglu: a gate|up pair.
+    "lora": the adapter GEMV pair (SVLA_LORA_DECODE_KERNELS, shapes svla_lora_gemv_down / svla_lora_gemv take).
+    "fp8": svla_gemv_mxfp8 on the e4m3 copy (fp8_decode_ok; the GeGLU pair splits the copy into two equal halves).
+    "lora_fp8": the adapter pair's projection half on the e4m3 copy (svla_lora_gemv_mxfp8, which has no prologue),
+    else svla_lora_gemv on the bf16 weights."""
+    sizes = [w.shape[0] for w in weights]
+    if form == "lora":
+        return (LORA_DECODE_KERNELS[0] and all(w.stride(1) == 1 for w in weights)
+                and K.lora_gemv_ok(M, k, sizes, norm))
+    halves = not geglu or sizes[0] == sizes[1]
+    if form == "lora_fp8":
+        return fp8_decode_ok(M, k, weights) and K.lora_gemv_mxfp8_ok(M, k, sizes) and halves
+    return fp8_decode_ok(M, k, weights, norm=norm) and halves
 
 
-def _lora_fp8_decode_ok(x_rows, k, weights) -> bool:
-    """Whether the projection half of an adapter decode step (after svla_lora_gemv_down) streams the e4m3 copy:
-    shapes svla_lora_gemv_mxfp8 takes, else svla_lora_gemv on the bf16 weights."""
-    return fp8_decode_ok(x_rows, k, weights) and K.lora_gemv_mxfp8_ok(x_rows, k, [w.shape[0] for w in weights])
+def _adapters(lora, lo, hi):
+    """Projections lo..hi-1 of lora = (r, scaling, (A, B) per projection) as decode_proj takes them, or None."""
+    return None if lora is None else (lora[0], lora[1], [A for A, _ in lora[2 + lo:2 + hi]],
+                                      [B for _, B in lora[2 + lo:2 + hi]])
 
 
-def _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora, f8d=None):
-    """gemma_attention_cached with an adapter on each of q, k, v, o: lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv),
-    (Ao, Bo)).  Prefill: the uncached adapter forward's kernels (GemmaAttentionLoRAFn) with the RoPE + cache fill of
-    the base prefill; decode: the adapter GEMVs, or their composition.  f8d (enable_fp8_lora_decode): the adapter
-    GEMVs' projection half streams the e4m3 copies of the frozen base weights (svla_lora_gemv_mxfp8)."""
-    r, s, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo) = lora
-    ops = _lora_ops()
-    if pre is not None:
-        if p0 == 0:
-            raise ValueError("gemma_attention_cached: the fused norm prologue is a decode-step path (p0 > 0)")
-        M, H = pre[1].shape
-        like = pre[1]
-    else:
-        x = _c(x)
-        M, H = x.shape
-        like = x
-    B, Lq = cfg.B, cfg.L
-    qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
-    R = K.lora_R(r)
-    qkv = _empty(M, qd + 2 * kd, like=like)
-    attn = _empty(M, qd, like=like)
-    if cos.shape[0] != B * Lq:
-        cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
-    if p0 > 0 and _lora_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
-        t = _empty(M, 3 * R, like=like)
-        if pre is not None:  # the norm pair in the prologue of the rank-r GEMV, which also stores x for the projection
-            x = _empty(M, H, like=like)
-        K.lora_gemv_down(x, [Aq, Ak, Av], r, t, norm=pre)
-        if f8d is not None and _lora_fp8_decode_ok(M, H, [wq, wk, wv]):
-            K.lora_gemv_mxfp8(x, *f8d.get("qkv", [wq, wk, wv]), t, [Bq, Bk, Bv], r, s, qkv)
+def decode_proj(x, weights, out, geglu_out=None, lora=None, f8d=None, site=None, batched=False, decode=True):
+    """out = x @ cat(weights)^T for one projection of a KV-cached step, on the first of these that applies:
+      1. batched: svla_gemm_skinny.
+      2. adapters, a decode step, decode_proj_ok("lora"): svla_lora_gemv_down (norm pair in its prologue), then
+         svla_lora_gemv_mxfp8 on f8d.get(site, weights) if a holder is given and decode_proj_ok("lora_fp8"), else
+         svla_lora_gemv.
+      3. adapters otherwise: the composition (add_rmsnorm2_fwd, then _lora_ops().down, linear_fwd, .up).
+      4. a holder, a decode step, decode_proj_ok("fp8"): svla_gemv_mxfp8 (norm pair in its prologue).
+      5. a norm prologue: svla_gemv_rmsnorm2.
+      6. linear_fwd.
+    x: the input rows, or pre = (res, y, w1, w2, eps1, eps2, h_out) when the norm pair rms(res + rms(y; w1); w2) is
+    formed in the prologue.  geglu_out = (g, u): weights is a gate|up pair and out its GeGLU.  lora = (r, scaling, As,
+    Bs); f8d: an FP8DecodeWeights and the `site` its copy is kept under ("qkv", "o", "gate_up", "down"); decode: p0 > 0.
+    Returns the x the adapter rules worked on (under pre they store it), else None."""
+    pre = x if isinstance(x, tuple) else None
+    like = pre[1] if pre is not None else x
+    M, k = like.shape
+    norm, geglu = pre is not None, geglu_out is not None
+    if batched:
+        K.gemm_skinny(x, weights, out)
+    elif lora is not None:
+        r, s, As, Bs = lora
+        if decode and decode_proj_ok("lora", M, k, weights, norm):
+            t = _empty(M, len(As) * K.lora_R(r), like=like)
+            if norm:  # the norm pair in the prologue of the rank-r GEMV, which also stores x for the projection
+                x = _empty(M, k, like=like)
+            K.lora_gemv_down(x, As, r, t, norm=pre)
+            if f8d is not None and decode_proj_ok("lora_fp8", M, k, weights, geglu=geglu):
+                K.lora_gemv_mxfp8(x, *f8d.get(site, weights), t, Bs, r, s, out, geglu_out=geglu_out)
+            else:
+                K.lora_gemv(x, weights, t, Bs, r, s, out, geglu_out=geglu_out)
         else:
-            K.lora_gemv(x, [wq, wk, wv], t, [Bq, Bk, Bv], r, s, qkv)
+            if geglu:
+                raise ValueError("decode_proj: the composed adapter form has no GeGLU (GemmaMLPLoRAFn runs that MLP)")
+            ops = _lora_ops()
+            if norm:
+                x = _empty(M, k, like=like)
+                K.add_rmsnorm2_fwd(*pre, x)
+            t = ops.down(x, As, r)
+            K.linear_fwd(x, weights, out)
+            ops.up(out, t, Bs, r, s)
+        return x
+    elif f8d is not None and decode and decode_proj_ok("fp8", M, k, weights, norm, geglu):
+        K.gemv_mxfp8(None if norm else x, *f8d.get(site, weights), out, geglu_out=geglu_out, norm=pre)
+    elif norm:
+        K.gemv_rmsnorm2(*pre, weights, out, geglu_out=geglu_out)
     else:
-        if pre is not None:
-            x = _empty(M, H, like=like)
-            K.add_rmsnorm2_fwd(*pre, x)
-        t = ops.down(x, [Aq, Ak, Av], r)
-        K.linear_fwd(x, [wq, wk, wv], qkv)
-        ops.up(qkv, t, [Bq, Bk, Bv], r, s)
-    if p0 > 0:
-        if DECODE_FUSED[0]:
-            K.attn_decode_rope(qkv, Lq, cos, sin, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
-                               cfg.softcap, kv_class, cfg.window, attn)
-        else:
-            K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, p0)
-            K.attn_decode(qkv[:, :qd], Lq, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
-                          cfg.softcap, kv_class, cfg.window, attn)
-    else:
-        K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, 0, k_back=True)
-        lse = _empty(B, cfg.Hq, Lq, dtype=F32, like=like)
-        cls = kv_class[:, :Lq].contiguous()  # held until the launch: attn_args keeps only its pointer
-        a = K.attn_args(B, Lq, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
-                        qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, cls, cfg.window)
-        K.attn_fwd(a, attn, lse)
-    out = _empty(M, wo.shape[0], like=like)
-    if p0 > 0 and _lora_decode_ok(M, qd, [wo]):
-        t_o = _empty(M, R, like=like)
-        K.lora_gemv_down(attn, [Ao], r, t_o)
-        if f8d is not None and _lora_fp8_decode_ok(M, qd, [wo]):
-            K.lora_gemv_mxfp8(attn, *f8d.get("o", [wo]), t_o, [Bo], r, s, out)
-        else:
-            K.lora_gemv(attn, [wo], t_o, [Bo], r, s, out)
-    else:
-        t_o = ops.down(attn, [Ao], r)
-        K.linear_fwd(attn, [wo], out)
-        ops.up(out, t_o, [Bo], r, s)
-    return out
+        K.linear_fwd(x, weights, out)
+    return None
 
 
 # Batched decode (enable_batched_decode): the window of new token rows B * Lq of a KV-cached step whose q|k|v and o
@@ -838,79 +832,77 @@ def gemma_attention_cached(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_cla
     (p0 == 0) runs the flash kernel of the uncached forward over the prompt, so it is bit-identical to it;
     later steps run the decode kernel over the first p0+L cache rows.  pre = (res, y, w1, w2, eps1, eps2, h_out): a
     decode step whose input x = rms(res + rms(y; w1); w2) is formed inside the q|k|v GEMV (h_out the new residual).
-    lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections.
-    f8d: the layer's FP8DecodeWeights (enable_fp8_decode) -- a decode step (p0 > 0) then streams the e4m3 copies of
-    q|k|v and o (svla_gemv_mxfp8); the prefill never reads them, and shapes the kernel refuses keep the bf16 GEMV.
-    lora and f8d together (enable_fp8_lora_decode): each adapter GEMV pair of a decode step is svla_lora_gemv_down +
-    svla_lora_gemv_mxfp8.
-    batched (enable_batched_decode, batched_decode_ok): a decode step whose q|k|v and o projections are
-    svla_gemm_skinny; never with pre, lora or f8d."""
+    lora = (r, scaling, (Aq, Bq), (Ak, Bk), (Av, Bv), (Ao, Bo)): unmerged adapters on the four projections; their
+    prefill is the uncached adapter forward's kernels (GemmaAttentionLoRAFn) with the RoPE + cache fill launch.
+    f8d: the layer's FP8DecodeWeights (enable_fp8_decode; with lora: enable_fp8_lora_decode), read by decode steps
+    only.  batched (enable_batched_decode, batched_decode_ok): never with pre, lora or f8d.
+    decode_proj states which kernel runs q|k|v and o under each of these."""
     if batched and (p0 == 0 or pre is not None or lora is not None or f8d is not None):
         raise ValueError("gemma_attention_cached: batched is a plain bf16 decode step (p0 > 0, no pre / lora / f8d)")
-    if lora is not None:
-        # the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term needs T
-        # complete before the projection starts, which inside one launch would take a grid barrier
-        return _attention_cached_lora(x, wq, wk, wv, wo, cos, sin, k_cache, v_cache, kv_class, p0, cfg, pre, lora, f8d)
     if pre is not None:
         if p0 == 0:
             raise ValueError("gemma_attention_cached: the fused norm prologue is a decode-step path (p0 > 0)")
-        M, H = pre[1].shape
         like = pre[1]
     else:
-        x = _c(x)
-        M, H = x.shape
-        like = x
+        x = like = _c(x)
+    M = like.shape[0]
     B, Lq = cfg.B, cfg.L
     qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
     qkv = _empty(M, qd + 2 * kd, like=like)
     attn = _empty(M, qd, like=like)
-    if p0 > 0:
-        # decode step: plain projection, then one launch rotates q / k, appends k / v to the cache and attends;
-        # the kernels read table row b*Lq+t (per-sequence positions), so a shared table is repeated per sequence
-        if cos.shape[0] != B * Lq:
-            cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
-        if batched:
-            K.gemm_skinny(x, [wq, wk, wv], qkv)
-        elif f8d is not None and fp8_decode_ok(M, H, [wq, wk, wv], norm=pre is not None):
-            K.gemv_mxfp8(x, *f8d.get("qkv", [wq, wk, wv]), qkv, norm=pre)
-        elif pre is not None:
-            K.gemv_rmsnorm2(*pre, [wq, wk, wv], qkv)
-        else:
-            K.linear_fwd(x, [wq, wk, wv], qkv)
-        if DECODE_FUSED[0]:
-            K.attn_decode_rope(qkv, Lq, cos, sin, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
-                               cfg.softcap, kv_class, cfg.window, attn)
-        else:
-            K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, p0)
-            K.attn_decode(qkv[:, :qd], Lq, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
-                          cfg.softcap, kv_class, cfg.window, attn)
-    elif PREFILL_ROPE_FILL[0]:
-        # the plain projection, then one launch rotates q and k in place and fills cache rows 0.. with k and v
-        # (svla_qkv_rope_fill: the ROPE epilogue's rounding, bitwise), instead of the RoPE epilogue + two cache copies
-        if cos.shape[0] != B * Lq:
-            cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
-        K.linear_fwd(x, [wq, wk, wv], qkv)
-        K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, 0, k_back=True)
-    else:
+    # the prefill's RoPE in the q|k|v GEMM's epilogue (the base path with SVLA_PREFILL_ROPE_FILL=0; the adapter term
+    # is added after the projection, so the adapter prefill always rotates afterwards)
+    rope_epilogue = p0 == 0 and lora is None and not PREFILL_ROPE_FILL[0]
+    if rope_epilogue:
         K.linear_fwd(x, [wq, wk, wv], qkv, kind=L.EPI_ROPE, rope=(cos, sin, cos.shape[0], cfg.D, qd + kd))
-        k_cache[:, :Lq].copy_(qkv[:, qd:qd + kd].view(B, Lq, kd))
-        v_cache[:, :Lq].copy_(qkv[:, qd + kd:].view(B, Lq, kd))
-    if p0 == 0:
-        lse = _empty(B, cfg.Hq, Lq, dtype=F32, like=like)
-        cls = kv_class[:, :Lq].contiguous()  # held until the launch: attn_args keeps only its pointer
-        a = K.attn_args(B, Lq, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
-                        qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, cls, cfg.window)
-        K.attn_fwd(a, attn, lse)
-    if skip_o:  # the caller runs the o projection (gemma_mlp_decode with o=(attn, wo): inside its launch)
+    else:
+        # the RoPE / cache kernels read table row b*Lq+t (per-sequence positions): a shared table is repeated
+        if cos.shape[0] != B * Lq:
+            cos, sin = cos.repeat(B, 1), sin.repeat(B, 1)
+        decode_proj(pre if pre is not None else x, [wq, wk, wv], qkv, lora=_adapters(lora, 0, 3), f8d=f8d, site="qkv",
+                    batched=batched, decode=p0 > 0)
+    if p0 > 0:
+        _decode_attention(qkv, attn, cos, sin, k_cache, v_cache, kv_class, p0, cfg)
+    else:
+        _prefill_attention(qkv, attn, cos, sin, k_cache, v_cache, kv_class, cfg, rotated=rope_epilogue)
+    # with adapters the o projection stays its own GEMV pair (skip_o / DECODE_O_FUSED do not apply): its adapter term
+    # needs T complete before the projection starts, which inside one launch would take a grid barrier
+    if skip_o and lora is None:  # the caller runs the o projection (gemma_mlp_decode with o=(attn, wo))
         return attn
     out = _empty(M, wo.shape[0], like=like)
-    if batched:
-        K.gemm_skinny(attn, [wo], out)
-    elif p0 > 0 and f8d is not None and fp8_decode_ok(M, qd, [wo]):
-        K.gemv_mxfp8(attn, *f8d.get("o", [wo]), out)
-    else:
-        K.linear_fwd(attn, [wo], out)
+    decode_proj(attn, [wo], out, lora=_adapters(lora, 3, 4), f8d=f8d, site="o", batched=batched, decode=p0 > 0)
     return out
+
+
+def _decode_attention(qkv, attn, cos, sin, k_cache, v_cache, kv_class, p0, cfg):
+    """A decode step's attention over the projected rows: one launch rotates q / k, appends k / v to the cache at
+    rows p0.. and attends (DECODE_FUSED), or the two-launch form."""
+    Lq = cfg.L
+    if DECODE_FUSED[0]:
+        K.attn_decode_rope(qkv, Lq, cos, sin, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
+                           cfg.softcap, kv_class, cfg.window, attn)
+    else:
+        K.qkv_rope_append(qkv, cfg.B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, p0)
+        K.attn_decode(qkv[:, :cfg.Hq * cfg.D], Lq, k_cache, v_cache, p0 + Lq, cfg.Hq, cfg.Hkv, cfg.D, cfg.scale,
+                      cfg.softcap, kv_class, cfg.window, attn)
+
+
+def _prefill_attention(qkv, attn, cos, sin, k_cache, v_cache, kv_class, cfg, rotated):
+    """The prefill's RoPE, cache fill and flash attention over the projected rows.  One launch rotates q and k in
+    place and fills cache rows 0.. with k and v (svla_qkv_rope_fill: the ROPE epilogue's rounding, bitwise); rotated:
+    the projection's epilogue did the RoPE, two copies fill the cache."""
+    B, Lq = cfg.B, cfg.L
+    qd, kd = cfg.Hq * cfg.D, cfg.Hkv * cfg.D
+    if rotated:
+        k_cache[:, :Lq].copy_(qkv[:, qd:qd + kd].view(B, Lq, kd))
+        v_cache[:, :Lq].copy_(qkv[:, qd + kd:].view(B, Lq, kd))
+    else:
+        K.qkv_rope_append(qkv, B, Lq, cfg.Hq, cfg.Hkv, cfg.D, cos, sin, k_cache, v_cache, 0, k_back=True)
+    lse = _empty(B, cfg.Hq, Lq, dtype=F32, like=qkv)
+    cls = kv_class[:, :Lq].contiguous()  # held until the launch: attn_args keeps only its pointer
+    a = K.attn_args(B, Lq, cfg.Hq, cfg.Hkv, cfg.D, qkv[:, :qd], qkv.stride(0), qkv[:, qd:qd + kd],
+                    qkv.stride(0), qkv[:, qd + kd:], qkv.stride(0), cfg.scale, cfg.softcap, cls, cfg.window)
+    K.attn_fwd(a, attn, lse)
 
 
 # the prefill's q|k|v: plain GEMM + svla_qkv_rope_fill (one launch: RoPE of q and k, cache rows of k and v) instead
@@ -944,16 +936,12 @@ def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora
     gate|up GeGLU GEMV, then the (split-K) down GEMV, both svla_gemv_mxfp8; not combined with `o`.  With `lora`
     (enable_fp8_lora_decode) the adapter form keeps its four launches and svla_lora_gemv_mxfp8 streams the e4m3 copies
     of gate|up and down."""
-    if f8d is not None and lora is None and o is None:
-        M, H = y.shape
-        I = wg.shape[0]
-        if fp8_decode_ok(M, H, [wg, wu], norm=True) and fp8_decode_ok(M, I, [wd]) and wu.shape[0] == I:
-            hact, g, u = (_empty(M, I, like=y) for _ in range(3))
-            K.gemv_mxfp8(None, *f8d.get("gate_up", [wg, wu]), hact, geglu_out=(g, u),
-                         norm=(res, y, w1, w2, eps1, eps2, h_out))
-            out = _empty(M, wd.shape[0], like=y)
-            K.gemv_mxfp8(hact, *f8d.get("down", [wd]), out)
-            return out
+    I = wg.shape[0]
+
+    def both(form):  # a joint choice: gate|up and down both run on the form's kernels, or the form is not taken
+        return (decode_proj_ok(form, y.shape[0], y.shape[1], [wg, wu], norm=True, geglu=True)
+                and decode_proj_ok(form, y.shape[0], I, [wd]))
+
     if lora is not None:
         # With adapters neither the persistent svla_decode_mlp nor DECODE_O_FUSED is used: each adapter term needs T
         # (a reduction over the whole input row) complete between the rank-r GEMV and the projection that adds it,
@@ -961,46 +949,33 @@ def gemma_mlp_decode(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, o=None, lora
         # the cheaper barrier (the persistent kernel's one barrier already costs what it saves on the o projection).
         if o is not None:
             raise ValueError("gemma_mlp_decode: the o projection inside the MLP launch is not built with adapters")
-        r, s, (Ag, Bg), (Au, Bu), (Ad, Bd) = lora
-        M, H = y.shape
-        I = wg.shape[0]
-        R = K.lora_R(r)
-        x = _empty(M, H, like=y)
-        if _lora_decode_ok(M, H, [wg, wu], norm=True) and _lora_decode_ok(M, I, [wd]):
-            t = _empty(M, 2 * R, like=y)
-            K.lora_gemv_down(x, [Ag, Au], r, t, norm=(res, y, w1, w2, eps1, eps2, h_out))
-            hact, g, u = (_empty(M, I, like=y) for _ in range(3))
-            if f8d is not None and _lora_fp8_decode_ok(M, H, [wg, wu]) and wu.shape[0] == I:
-                K.lora_gemv_mxfp8(x, *f8d.get("gate_up", [wg, wu]), t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
-            else:
-                K.lora_gemv(x, [wg, wu], t, [Bg, Bu], r, s, hact, geglu_out=(g, u))
-            t_d = _empty(M, R, like=y)
-            K.lora_gemv_down(hact, [Ad], r, t_d)
-            out = _empty(M, wd.shape[0], like=y)
-            if f8d is not None and _lora_fp8_decode_ok(M, I, [wd]):
-                K.lora_gemv_mxfp8(hact, *f8d.get("down", [wd]), t_d, [Bd], r, s, out)
-            else:
-                K.lora_gemv(hact, [wd], t_d, [Bd], r, s, out)
+        if not both("lora"):  # the norm pair, then the uncached adapter forward's kernels
+            r, s, (Ag, Bg), (Au, Bu), (Ad, Bd) = lora
+            x = torch.empty_like(y)
+            K.add_rmsnorm2_fwd(res, y, w1, w2, eps1, eps2, h_out, x)
+            return GemmaMLPLoRAFn.apply(x, wg, wu, wd, s, r, Ag, Bg, Au, Bu, Ad, Bd)
+    elif f8d is None or o is not None or not both("fp8"):
+        f8d = None  # the bf16 forms: the persistent launch (with or without o), else the pair below
+        if o is not None:  # y = attn @ wo^T (the o projection), in the persistent launch or as its own GEMV
+            attn, wo = o
+            y = _empty(attn.shape[0], wo.shape[0], like=attn)
+            if (not persist_ok(y, wg, wu, wd) or attn.shape[1] > 2048 or wo.stride(1) != 1
+                    or y.shape[1] > 8 * K.decode_mlp_grid(y.shape[0], y.shape[1], wg.shape[0])):
+                decode_proj(attn, [wo], y)
+                o = None
+        if persist_ok(y, wg, wu, wd):
+            out = _empty(y.shape[0], wd.shape[0], like=y)
+            hact = _empty(y.shape[0], I, like=y)
+            K.decode_mlp(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, hact, out, o=o)  # one launch, bitwise
             return out
-        K.add_rmsnorm2_fwd(res, y, w1, w2, eps1, eps2, h_out, x)
-        return GemmaMLPLoRAFn.apply(x, wg, wu, wd, s, r, Ag, Bg, Au, Bu, Ad, Bd)
-    if o is not None:  # y = attn @ wo^T (the o projection), in the persistent launch or as its own GEMV
-        attn, wo = o
-        y = _empty(attn.shape[0], wo.shape[0], like=attn)
-        if (not persist_ok(y, wg, wu, wd) or attn.shape[1] > 2048 or wo.stride(1) != 1
-                or y.shape[1] > 8 * K.decode_mlp_grid(y.shape[0], y.shape[1], wg.shape[0])):
-            K.linear_fwd(attn, [wo], y)
-            o = None
+    # two projections: the norm-prologue gate|up GeGLU, then down -- adapter GEMV pairs (four launches), svla_gemv_mxfp8
+    # on the e4m3 copies, or svla_gemv_rmsnorm2 + the bf16 GEMV
     M = y.shape[0]
-    I = wg.shape[0]
-    out = _empty(M, wd.shape[0], like=y)
-    if persist_ok(y, wg, wu, wd):
-        hact = _empty(M, I, like=y)
-        K.decode_mlp(res, y, w1, w2, eps1, eps2, h_out, wg, wu, wd, hact, out, o=o)  # one persistent launch, bitwise
-        return out
     hact, g, u = (_empty(M, I, like=y) for _ in range(3))
-    K.gemv_rmsnorm2(res, y, w1, w2, eps1, eps2, h_out, [wg, wu], hact, geglu_out=(g, u))
-    K.linear_fwd(hact, [wd], out)
+    decode_proj((res, y, w1, w2, eps1, eps2, h_out), [wg, wu], hact, geglu_out=(g, u), lora=_adapters(lora, 0, 2),
+                f8d=f8d, site="gate_up")
+    out = _empty(M, wd.shape[0], like=y)
+    decode_proj(hact, [wd], out, lora=_adapters(lora, 2, 3), f8d=f8d, site="down")
     return out
 
 
@@ -2153,12 +2128,20 @@ def lm_head_fp8_decode(h, w, target, cap, stash, f8d: FP8DecodeWeights):
     streams the copy once and leaves the softcapped logits and the statistics, then svla_ce_finalize.  Returns
     (logits [M, V] view, loss)."""
     h = _c(h)
-    M, V = h.shape[0], w.shape[0]
     (wq,), (ws,) = f8d.get("lm_head", [w])
+    return _decode_head(h, w.shape[0], target, stash,
+                        lambda logits_buf, V, stats: K.head_gemv_mxfp8(h, wq, ws, logits_buf, V, stats, cap))
+
+
+def _decode_head(h, V, target, stash, stream_lm_head):
+    """The part every decode head shares: stream_lm_head(logits_buf, V, stats) passes over lm_head once and leaves the
+    softcapped logits and the per-tile statistics, svla_ce_finalize turns those into lse, argmax and the loss, and the
+    stash gets what LMHeadCEFn leaves there.  Returns (logits [M, V] view, loss)."""
+    M = h.shape[0]
     logits_buf = _empty(M, K.round_up(V, 64), like=h)
     ntn = K.ceil_div(V, 128)
     stats = _empty(M, ntn, 3, dtype=F32, like=h)
-    K.head_gemv_mxfp8(h, wq, ws, logits_buf, V, stats, cap)
+    stream_lm_head(logits_buf, V, stats)
     lse = _empty(M, dtype=F32, like=h)
     argmax = _empty(M, dtype=torch.int64, like=h)
     loss_rows = _empty(M, dtype=F32, like=h)
@@ -2184,26 +2167,17 @@ def lm_head_lora_decode(h, w, target, cap, stash, scaling, r, A, B, f8d: Optiona
     copy of lm_head is streamed instead (svla_lora_head_gemv_mxfp8) where that kernel takes the width.  Returns
     (logits [M, V] view, loss)."""
     h = _c(h)
-    M, V = h.shape[0], w.shape[0]
+    M = h.shape[0]
     t = _empty(M, K.lora_R(r), like=h)
     K.lora_gemv_down(h, [A], r, t)
-    logits_buf = _empty(M, K.round_up(V, 64), like=h)
-    ntn = K.ceil_div(V, 128)
-    stats = _empty(M, ntn, 3, dtype=F32, like=h)
-    if f8d is not None and K.lora_head_gemv_mxfp8_ok(M, h.shape[1], r):
-        (wq,), (ws,) = f8d.get("lm_head", [w])
-        K.lora_head_gemv_mxfp8(h, wq, ws, t, B, r, scaling, logits_buf, V, stats, cap)
-    else:
-        K.lora_head_gemv(h, w, t, B, r, scaling, logits_buf, V, stats, cap)
-    lse = _empty(M, dtype=F32, like=h)
-    argmax = _empty(M, dtype=torch.int64, like=h)
-    loss_rows = _empty(M, dtype=F32, like=h)
-    loss2 = _empty(2, dtype=F32, like=h)
-    K.ce_finalize(V, ntn, stats, logits_buf[:, :V], target, lse, argmax, loss_rows, loss2)
-    stash["argmax"] = argmax
-    stash["lse"] = lse
-    stash["n_valid"] = loss2[1:2]
-    return logits_buf[:, :V], loss2[0]
+
+    def stream_lm_head(logits_buf, V, stats):
+        if f8d is not None and K.lora_head_gemv_mxfp8_ok(M, h.shape[1], r):
+            (wq,), (ws,) = f8d.get("lm_head", [w])
+            K.lora_head_gemv_mxfp8(h, wq, ws, t, B, r, scaling, logits_buf, V, stats, cap)
+        else:
+            K.lora_head_gemv(h, w, t, B, r, scaling, logits_buf, V, stats, cap)
+    return _decode_head(h, w.shape[0], target, stash, stream_lm_head)
 
 
 # ------------------------------------------------------------------------------------ attention plug-in

@@ -141,6 +141,12 @@ def _lora_args(ads):
     return (ads[0].r, ads[0].scaling, *[(a.A.detach(), a.B.detach()) for a in ads])
 
 
+def _decode_holder(adapters, fp8, fp8_lora):
+    """The FP8DecodeWeights a decode step streams for a sublayer or the head: with adapters on it the frozen holder of
+    enable_fp8_lora_decode, else the holder of enable_fp8_decode (either may be None: the bf16 weights)."""
+    return fp8_lora if adapters is not None else fp8
+
+
 class Gemma2MLP(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -234,6 +240,7 @@ class Gemma2Attention(nn.Module):
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=False)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
         self.rotary_emb = Gemma2RotaryEmbedding(self.head_dim, self.max_position_embeddings, self.rope_theta)
+        self._svla_lora_decode = False  # Gemma2Model.enable_lora_decode
 
     def attn_cfg(self, B: int, Lq: int) -> "Fn.GemmaAttnCfg":
         return Fn.GemmaAttnCfg(B, Lq, self.num_heads, self.num_key_value_heads, self.head_dim, self.scaling,
@@ -245,7 +252,7 @@ class Gemma2Attention(nn.Module):
         cfg = self.attn_cfg(B, Lq)
         cos, sin = rope
         ads = _lora_of(self.q_proj, self.k_proj, self.v_proj, self.o_proj)
-        if ads and cache is not None and not getattr(self, "_svla_lora_decode", False):
+        if ads and cache is not None and not self._svla_lora_decode:
             raise RuntimeError(LORA_MERGE_MSG)
         if cache is not None:
             i = self.layer_idx
@@ -306,6 +313,23 @@ class Gemma2DecoderLayer(nn.Module):
         self.pre_feedforward_layernorm = Gemma2RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_feedforward_layernorm = Gemma2RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.sliding_window = config.sliding_window
+        # the e4m3 decode copies (Fn.FP8DecodeWeights) of Gemma2Model.enable_fp8_decode / enable_fp8_lora_decode
+        self._svla_fp8_decode = None
+        self._svla_fp8_lora_decode = None
+
+    def decode_plan(self):
+        """What a fused decode step (Gemma2Model._decode_fused) hands this layer's two sublayers: (adapters of the
+        attention, adapters of the MLP, holder for the attention, holder for the MLP, fuse_o).  The holder of
+        enable_fp8_decode is never used beside adapters; the one of enable_fp8_lora_decode goes to the sublayers that
+        carry them.  fuse_o: the o projection inside the MLP's launch (never with adapters, whose term needs its own
+        launch boundary, or e4m3 copies)."""
+        at, mlp = self.self_attn, self.mlp
+        la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))
+        lm = _lora_args(_lora_of(mlp.gate_proj, mlp.up_proj, mlp.down_proj))
+        f8d = self._svla_fp8_decode if la is None and lm is None else None
+        fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None and f8d is None
+        return (la, lm, _decode_holder(la, f8d, self._svla_fp8_lora_decode),
+                _decode_holder(lm, f8d, self._svla_fp8_lora_decode), fuse_o)
 
     def set_fp8_projections(self, enabled: bool):
         """BASELINE configs[4]: run the forward q|k|v, o, gate|up and down projections of this layer on the fp8
@@ -396,7 +420,7 @@ class Gemma2Model(nn.Module):
 
     @property
     def fp8_decode(self) -> bool:
-        return getattr(self.layers[0], "_svla_fp8_decode", None) is not None
+        return self.layers[0]._svla_fp8_decode is not None
 
     def enable_fp8_lora_decode(self, enabled: bool = True):
         """Weight-only MX fp8 decode under unmerged adapters (opt-in, on top of enable_lora_decode): the projection half
@@ -409,7 +433,7 @@ class Gemma2Model(nn.Module):
 
     @property
     def fp8_lora_decode(self) -> bool:
-        return getattr(self.layers[0], "_svla_fp8_lora_decode", None) is not None
+        return self.layers[0]._svla_fp8_lora_decode is not None
 
     def enable_batched_decode(self, enabled: bool = True):
         """Batched decode (opt-in, default off): a KV-cached step that adds more than 8 token rows (B * Lq inside
@@ -505,39 +529,22 @@ class Gemma2Model(nn.Module):
                 and H <= Kn.GEMV_NORM_MAX_K and H % 8 == 0
                 and (self.fp8_decode or all(getattr(l.mlp, "_svla_fp8", None) is None for l in layers))):
             return self._decode_fused(res, shp, rope, cache)
-        if self._batched_decode_ok(res.shape[0], cache.seen_tokens):
-            return self._decode_batched(res, shp, rope, cache)
-        x = layers[0].input_layernorm(res)
-        for i, layer in enumerate(layers):
-            a = layer.self_attn(x.view(shp), attention_mask, rope, cache).reshape(-1, H)
-            pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
-            h, x = torch.empty_like(res), torch.empty_like(res)
-            Kn.add_rmsnorm2_fwd(res, a, pa.weight, pf.weight, pa.eps, pf.eps, h, x)
-            m = layer.mlp(x).reshape(-1, H)
-            nxt = layers[i + 1].input_layernorm if i + 1 < len(layers) else self.norm
-            po = layer.post_feedforward_layernorm
-            res, x = torch.empty_like(res), torch.empty_like(res)
-            Kn.add_rmsnorm2_fwd(h, m, po.weight, nxt.weight, po.eps, nxt.eps, res, x)
-        cache.seen_tokens += shp[1]
-        return x.view(shp)
-
-
-    def _decode_batched(self, res, shp, rope, cache):
-        """A batched decode step (enable_batched_decode, Fn.batched_decode_ok): _forward_cached's unfused loop with
-        q|k|v and o on svla_gemm_skinny; everything else in it is that loop's."""
-        layers = self.layers[: self.config.num_hidden_layers]
+        # a batched decode step (enable_batched_decode, Fn.batched_decode_ok) is this loop with q|k|v and o on
+        # svla_gemm_skinny; everything else in it is the same
+        batched = self._batched_decode_ok(res.shape[0], cache.seen_tokens)
         B, Lq = shp[0], shp[1]
         cos, sin = rope
         x = layers[0].input_layernorm(res)
         for i, layer in enumerate(layers):
-            at, mlp = layer.self_attn, layer.mlp
+            at = layer.self_attn
+            la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))  # refused above with lora_decode off
             a = Fn.gemma_attention_cached(x, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight, at.o_proj.weight,
                                           cos, sin, cache.key_cache[i], cache.value_cache[i], cache.kv_class,
-                                          cache.seen_tokens, at.attn_cfg(B, Lq), batched=True)
+                                          cache.seen_tokens, at.attn_cfg(B, Lq), lora=la, batched=batched)
             pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
             h, x = torch.empty_like(res), torch.empty_like(res)
             Kn.add_rmsnorm2_fwd(res, a, pa.weight, pf.weight, pa.eps, pf.eps, h, x)
-            m = mlp(x).reshape(-1, x.shape[-1])
+            m = layer.mlp(x).reshape(-1, H)
             nxt = layers[i + 1].input_layernorm if i + 1 < len(layers) else self.norm
             po = layer.post_feedforward_layernorm
             res, x = torch.empty_like(res), torch.empty_like(res)
@@ -562,24 +569,16 @@ class Gemma2Model(nn.Module):
                 po = layers[i - 1].post_feedforward_layernorm
                 res = torch.empty_like(h)
                 pre = (h, m, po.weight, layer.input_layernorm.weight, po.eps, layer.input_layernorm.eps, res)
-            la = _lora_args(_lora_of(at.q_proj, at.k_proj, at.v_proj, at.o_proj))
-            lm = _lora_args(_lora_of(mlp.gate_proj, mlp.up_proj, mlp.down_proj))
-            # weight-only fp8 decode (enable_fp8_decode): the layer's e4m3 copies, never together with adapters --
-            # those take the holder of enable_fp8_lora_decode, in the sublayers that carry them
-            f8d = getattr(layer, "_svla_fp8_decode", None) if la is None and lm is None else None
-            f8l = getattr(layer, "_svla_fp8_lora_decode", None)
-            # o projection inside the MLP's launch (never with adapters: their term needs its own launch boundary)
-            fuse_o = Fn.DECODE_O_FUSED[0] and Fn.DECODE_MLP_PERSIST[0] and la is None and lm is None and f8d is None
+            la, lm, f8a, f8m, fuse_o = layer.decode_plan()
             a = Fn.gemma_attention_cached(x if i == 0 else None, at.q_proj.weight, at.k_proj.weight, at.v_proj.weight,
                                           at.o_proj.weight, cos, sin, cache.key_cache[i], cache.value_cache[i],
                                           cache.kv_class, cache.seen_tokens, at.attn_cfg(B, Lq), pre=pre,
-                                          skip_o=fuse_o, lora=la, f8d=f8d if la is None else f8l)
+                                          skip_o=fuse_o, lora=la, f8d=f8a)
             pa, pf = layer.post_attention_layernorm, layer.pre_feedforward_layernorm
             h = torch.empty_like(res)
             m = Fn.gemma_mlp_decode(res, None if fuse_o else a, pa.weight, pf.weight, pa.eps, pf.eps, h,
                                     mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
-                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm,
-                                    f8d=f8d if lm is None else f8l)
+                                    o=(a, at.o_proj.weight) if fuse_o else None, lora=lm, f8d=f8m)
         po = layers[-1].post_feedforward_layernorm
         res, x = torch.empty_like(h), torch.empty_like(h)
         Kn.add_rmsnorm2_fwd(h, m, po.weight, self.norm.weight, po.eps, self.norm.eps, res, x)
@@ -596,6 +595,9 @@ class Gemma2ForCausalLM(nn.Module):
         self.model = Gemma2Model(config)
         self.vocab_size = config.vocab_size
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
+        # the e4m3 decode copies of lm_head (Fn.FP8DecodeWeights) of enable_fp8_decode / enable_fp8_lora_decode
+        self._svla_fp8_decode_head = None
+        self._svla_fp8_lora_decode_head = None
 
     def get_input_embeddings(self):
         return self.model.embed_tokens
@@ -631,8 +633,7 @@ class Gemma2ForCausalLM(nn.Module):
 
     def fp8_decode_holders(self):
         """Every FP8DecodeWeights of the model (the layers', then the head's); [] with the switch off."""
-        hs = [getattr(l, "_svla_fp8_decode", None) for l in self.model.layers]
-        hs.append(getattr(self, "_svla_fp8_decode_head", None))
+        hs = [l._svla_fp8_decode for l in self.model.layers] + [self._svla_fp8_decode_head]
         return [h for h in hs if h is not None]
 
     def enable_fp8_lora_decode(self, enabled: bool = True):
@@ -643,8 +644,7 @@ class Gemma2ForCausalLM(nn.Module):
 
     def fp8_lora_decode_holders(self):
         """Every FP8DecodeWeights of enable_fp8_lora_decode (the layers', then the head's); [] with the switch off."""
-        hs = [getattr(l, "_svla_fp8_lora_decode", None) for l in self.model.layers]
-        hs.append(getattr(self, "_svla_fp8_lora_decode_head", None))
+        hs = [l._svla_fp8_lora_decode for l in self.model.layers] + [self._svla_fp8_lora_decode_head]
         return [h for h in hs if h is not None]
 
     def set_decoder(self, decoder):
@@ -704,14 +704,13 @@ class Gemma2ForCausalLM(nn.Module):
         ad = getattr(self.lm_head, "lora", None)  # add_lora("spatialvla-linear+emb+h"): the adapter on lm_head
         adapter = () if ad is None else (ad.scaling, ad.r, ad.A, ad.B)
         h2d = hidden_states.reshape(-1, hidden_states.shape[-1])
-        f8d = getattr(self, "_svla_fp8_decode_head", None) if decode and ad is None else None
-        f8l = getattr(self, "_svla_fp8_lora_decode_head", None) if decode else None  # enable_fp8_lora_decode
-        if ad is None and f8d is None:
-            f8d = f8l
-        if f8d is not None and self.lm_head.weight.stride(1) == 1 and Fn.lm_head_fp8_decode_ok(h2d):
+        # the e4m3 copy of lm_head, decode steps only; without an adapter either switch's serves the same kernel
+        f8l = self._svla_fp8_lora_decode_head if decode else None
+        f8d = _decode_holder(ad, (self._svla_fp8_decode_head or f8l) if decode else None, f8l)
+        if ad is None and f8d is not None and self.lm_head.weight.stride(1) == 1 and Fn.lm_head_fp8_decode_ok(h2d):
             return Fn.lm_head_fp8_decode(h2d, self.lm_head.weight, target, cap, stash, f8d)
         if ad is not None and Fn.lm_head_lora_decode_ok(h2d, ad.r):
             # a decode step's rows under the adapter: T, one pass over lm_head (svla_lora_head_gemv), finalize
-            return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter, f8d=f8l)
+            return Fn.lm_head_lora_decode(h2d, self.lm_head.weight, target, cap, stash, *adapter, f8d=f8d)
         return Fn.LMHeadCEFn.apply(hidden_states.reshape(-1, hidden_states.shape[-1]), self.lm_head.weight, target,
                                    cap, stash, *adapter)
